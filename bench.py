@@ -12,6 +12,8 @@ Prints ONE JSON line on rank 0 with the extra objects `roofline` (implicit-GEMM 
 stream in an instrumented eager pass of the same step), `step_ms` (median / p10 / p90 of the timed steps, HIP events),
 `extra_shapes` (the shipped script's grid-576 shape and a 384x576 image), at N>1 `allreduce_exposed_ms`, and at N=1
 `cpu_baseline` (the oracle's CPU restatement of the same step on the host's physical cores, bounded sample).
+--steps is the number of timed steps; --dump-outputs DIR then runs the timed path's step once more from the seeded starting state,
+untimed, and writes what it computed as .npy files (dump_step, dump_outputs).
 """
 import argparse
 import json
@@ -158,7 +160,6 @@ def self_launch(n):
     torch.distributed.run, one per GPU, rendezvous on 127.0.0.1.  Output and exit code are the ranks'."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")      # main + prefetch + weight-gradient + exchange streams + RCCL's own: more than HIP's default 4 queues
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd, env=env)
@@ -186,6 +187,51 @@ def timed_steps(step, n, barrier):
     barrier()
     dt = time.perf_counter() - t0
     return dt, [evs[i].elapsed_time(evs[i + 1]) for i in range(n)], out
+
+
+DUMP_SAMPLE_PER_TENSOR = 4096       # --dump-outputs: elements per trainable parameter in the parameter / gradient samples
+
+
+def seeded_state(trainer):
+    """The trainer's state before its first step: parameters (name-seeded), AdamW moments and scalars (step count, StepLR factor)."""
+    return [t.clone() for t in (trainer.flat_p, trainer.exp_avg, trainer.exp_avg_sq, trainer.opt_state)]
+
+
+def dump_step(trainer, step, seeded, barrier):
+    """--dump-outputs: after the timed steps, one more step of the timed path (the same `step`, the same batch, untimed) from the seeded
+    state.  The weight-gradient reductions sum in atomic order, so every step differs from run to run by rounding and ~40 AdamW steps
+    carry that into whole learning-rate units on near-zero gradients; from the seeded state the dumped step's inputs are the same every
+    run and its outputs differ by one step's rounding."""
+    barrier()
+    for dst, src in zip((trainer.flat_p, trainer.exp_avg, trainer.exp_avg_sq, trainer.opt_state), seeded):
+        dst.copy_(src)
+    out = step()
+    barrier()
+    return out
+
+
+def dump_outputs(trainer, out, path):
+    """--dump-outputs: what the dump step (dump_step) computed, as .npy files under `path` (rank 0).
+    <key>.npy: every entry of the step's returned dict (device scalars: the losses, the weighted total `loss`, `grad_norm`), float64.
+    params_sample.npy / grads_sample.npy (float32): the step also leaves the updated parameters and the step's gradient in the trainer's
+    flat arenas -- a fixed sample of both: per trainable parameter in name order, all of it up to DUMP_SAMPLE_PER_TENSOR elements, else
+    that many indices drawn by a generator seeded with the parameter's name (the same elements whatever the arena layout)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), torch.as_tensor(v).detach().to("cpu", torch.float64).numpy())
+    idx = []
+    for name in sorted(trainer.offsets):
+        off, sz = trainer.offsets[name]
+        if sz <= DUMP_SAMPLE_PER_TENSOR:
+            idx.append(torch.arange(off, off + sz))
+        else:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx.append(off + torch.randint(sz, (DUMP_SAMPLE_PER_TENSOR,), generator=g))
+    idx = torch.cat(idx).to(trainer.flat_p.device)
+    for fname, arena in (("params_sample", trainer.flat_p), ("grads_sample", trainer.flat_g)):
+        np.save(os.path.join(path, f"{fname}.npy"), arena[idx].to("cpu", torch.float32).numpy())
 
 
 def exchange_variants(trainer, step, barrier, dev, share, rank, n=5):
@@ -424,7 +470,14 @@ def main(argv=None):
     ap.add_argument("--no-prefetch", action="store_true",
                     help="graph mode: run the frozen stage (stem + layer1) of a batch inside its own step instead of beside the previous step's "
                          "matcher / backward (engine.Trainer: frozen-stage prefetch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed path's step once more from the seeded starting state (untimed) and write what "
+                         "it computed to DIR/<name>.npy: its returned losses, float64, and a fixed sample of the updated parameters and of the "
+                         "gradient, float32 (see dump_step / dump_outputs).  The same arguments give the same inputs, so two builds can be "
+                         "compared file for file (--mode graph or eager pins the launch mode that auto picks by timing)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps: at least one timed step")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus))
@@ -432,9 +485,6 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world > 1:
-        # (ranks started by an external launcher: the HIP runtime has not initialised yet -- nothing above touches the device)
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the Counting-DETR HIP path has no CPU fallback")
     if world != a.gpus:
@@ -459,6 +509,7 @@ def main(argv=None):
     if a.no_prefetch:
         os.environ["CDETR_FROZEN_PREFETCH"] = "0"
     trainer = build_trainer(dev, a.queries, a.prior, a.precision)
+    seeded = seeded_state(trainer) if a.dump_outputs else None
     Q = a.queries if a.prior == "learned" else int(round(a.queries ** 0.5)) ** 2
     images, rects, targets = synthetic_batch(a.batch, H, W, Ts, seed=1000 * rank, device=dev)
 
@@ -532,6 +583,10 @@ def main(argv=None):
         per_rank_ms = [float(x[0]) for x in allr]
     dt = float(t.item())
     loss = float(out["loss"])
+    if a.dump_outputs:
+        d_out = dump_step(trainer, step, seeded, barrier)
+        if rank == 0:
+            dump_outputs(trainer, d_out, a.dump_outputs)
     ms_per_step = dt / a.steps * 1e3
     value = a.batch * world * a.steps / dt
 

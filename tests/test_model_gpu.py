@@ -422,6 +422,41 @@ def test_bench_self_launches_two_ranks_rehearsal():
         assert r["value"] > 0 and r["step_ms"]["n"] == 3 and r["roofline"]["achieved"] > 0
 
 
+def test_bench_dump_outputs_of_the_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: one more step of the timed path from the seeded starting state -- its returned losses (float64) and
+    fixed samples of the updated parameters and the gradient (float32), at most 64 MB; --steps is the number of timed steps; a second run
+    with the same arguments dumps the same step to within one step's rounding (the weight-gradient reductions sum in atomic order)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "256", "256",
+                            "--queries", "100", "--mode", "graph", "--no-cpu-baseline", "--no-alt", "--no-extra", "--no-inference", "--no-real-data",
+                            "--dump-outputs", str(d)], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["steps"] == 2 and r["step_ms"]["n"] == 2
+        files = sorted(os.listdir(d))
+        assert {"loss.npy", "loss_ce.npy", "grad_norm.npy", "params_sample.npy", "grads_sample.npy"} <= set(files), files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 2 ** 20
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["params_sample"].shape == arrs["grads_sample"].shape and np.abs(arrs["grads_sample"]).max() > 0
+        runs.append(arrs)
+    for k in runs[0]:
+        a, b = runs[0][k], runs[1][k]
+        if k in ("params_sample", "grads_sample"):
+            np.testing.assert_allclose(b, a, rtol=1e-4, atol=1e-5 * float(np.abs(a).max()), err_msg=k)
+        else:
+            np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-7, err_msg=k)
+
+
 def test_fscd_lvis_train_epoch_and_infer(tmp_path):
     """BASELINE config 4 (FSCD-LVIS 2nd stage: the same network on the LVIS readers, L2/data/fscd_lvis.py) end to end on the tiny
     LVIS-shaped dataset: reader -> collate (different image sizes: padding mask; per-image exemplars, absent rows marked) -> prefetch ->
