@@ -91,6 +91,62 @@ def get_args_parser():
     return p
 
 
+def get_args_parser_stage1():
+    """The 1st-stage CLI (A1/main.py:27-132): A1's flags and defaults -- `defined` spatial prior and num_query_pattern 1 as the shipped
+    scripts pass them (A1/scripts/weakly_supervise_fscd_147.sh), epochs 30, lr_drop 20, seed 42 -- plus this build's additions."""
+    p = argparse.ArgumentParser("Counting-DETR 1st stage (MI355X)", add_help=True)
+    p.add_argument("--lr", default=1e-4, type=float)
+    p.add_argument("--lr_backbone_names", default=["backbone"], type=str, nargs="+")
+    p.add_argument("--lr_backbone", default=1e-5, type=float)
+    p.add_argument("--lr_linear_proj_names", default=[], type=str, nargs="+")
+    p.add_argument("--lr_linear_proj_mult", default=0.1, type=float)
+    p.add_argument("--batch_size", default=1, type=int, help="images per step (the reference: 1; more need equal exemplar counts)")
+    p.add_argument("--weight_decay", default=1e-4, type=float)
+    p.add_argument("--epochs", default=30, type=int)
+    p.add_argument("--lr_drop", default=20, type=int)
+    p.add_argument("--lr_drop_epochs", default=None, type=int, nargs="+")
+    p.add_argument("--clip_max_norm", default=0.1, type=float)
+    p.add_argument("--sgd", action="store_true", help="(not supported: AdamW only)")
+    p.add_argument("--vis_pseudo", action="store_true", help="(accepted for script compatibility; no visualisation is written)")
+    p.add_argument("--frozen_weights", type=str, default=None)
+    p.add_argument("--backbone", default="resnet50", type=str)
+    p.add_argument("--dilation", default=True, type=lambda s: str(s).lower() not in ("0", "false", "no"))
+    p.add_argument("--num_feature_levels", default=1, type=int)
+    p.add_argument("--enc_layers", default=6, type=int)
+    p.add_argument("--dec_layers", default=6, type=int)
+    p.add_argument("--dim_feedforward", default=1024, type=int)
+    p.add_argument("--hidden_dim", default=256, type=int)
+    p.add_argument("--dropout", default=0.0, type=float)
+    p.add_argument("--nheads", default=8, type=int)
+    p.add_argument("--num_query_position", default=300, type=int)
+    p.add_argument("--num_query_pattern", default=1, type=int)
+    p.add_argument("--spatial_prior", default="defined", choices=["learned", "grid", "defined"], type=str)
+    p.add_argument("--attention_type", default="RCDA", choices=["RCDA", "nn.MultiheadAttention"], type=str)
+    p.add_argument("--masks", action="store_true")
+    p.add_argument("--dataset_file", default="fscd_147", choices=["fscd_147", "fscd_147_point"])
+    p.add_argument("--data_path", default="./FSC147/", type=str)
+    p.add_argument("--output_dir", default="./outputs/fscd_147_1st_stage", type=str)
+    p.add_argument("--device", default="cuda")
+    p.add_argument("--seed", default=42, type=int)
+    p.add_argument("--resume", default="")
+    p.add_argument("--auto_resume", default=False, action="store_true")
+    p.add_argument("--start_epoch", default=0, type=int)
+    p.add_argument("--eval", action="store_true", help="validation loss of the model (A1/engine.py evaluate), then exit")
+    p.add_argument("--generate_pseudo_label", action="store_true", help="write pseudo_bbox_{train,val,test}.json, then exit")
+    p.add_argument("--num_workers", default=2, type=int)
+    p.add_argument("--cache_mode", default=False, action="store_true")
+    p.add_argument("--scale_factor", default=32, type=int)
+    # additions of this build
+    p.add_argument("--synthetic", action="store_true", help="train on seeded synthetic batches (no dataset needed)")
+    p.add_argument("--steps_per_epoch", default=20, type=int, help="synthetic mode only")
+    p.add_argument("--synthetic_size", default=[384, 576], type=int, nargs=2, help="synthetic mode only: image H W")
+    p.add_argument("--print_freq", default=100, type=int, help="the loss is read back every this many steps")
+    p.add_argument("--no_graph_cache", dest="graph_cache", action="store_false",
+                   help="train with the stream-ordered step instead of cached HIP graphs (one per padded image size / points shape)")
+    p.add_argument("--graph_cache_size", default=32, type=int)
+    return p
+
+
 def default_args(**kw):
     a = get_args_parser().parse_args([])
     a.aux_loss = False            # the shipped scripts all pass --no_aux_loss (A2/scripts/var_wh_laplace_600.sh:7)

@@ -174,6 +174,106 @@ class FSCDLVISDataset(Dataset):
                 "labels": torch.zeros([bboxes.shape[0]], dtype=torch.int64), "orig_size": np.array([img_h, img_w])}
 
 
+def _exemplar_centres_whs(anno):
+    """box_examples_coordinates -> exemplar centres and sizes in pixels, float32 [K,2] each (A1/datasets/fscd_147.py:37-49)."""
+    c, wh = [], []
+    for b in anno["box_examples_coordinates"]:
+        x1, y1, x2, y2 = b[0][0], b[0][1], b[2][0], b[2][1]
+        c.append([(x1 + x2) / 2, (y1 + y2) / 2])
+        wh.append([x2 - x1, y2 - y1])
+    return np.array(c, dtype=np.float32).reshape(-1, 2), np.array(wh, dtype=np.float32).reshape(-1, 2)
+
+
+class FSC147ExemplarDataset(Dataset):
+    """1st-stage training / validation reader (A1/datasets/fscd_147.py:11-73, FSCD147_Exemplars): the exemplar boxes of an image as
+    points (centres) + whs (sizes), both divided by the ORIGINAL image size; the image resized to floor(w/32)*32 x floor(h/32)*32 with
+    BILINEAR, ToTensor + ImageNet normalisation."""
+
+    def __init__(self, args, split="train"):
+        data_path = args.data_path
+        self.im_dir = os.path.join(data_path, "images_384_VarV2")
+        self.annotations = _load_json(os.path.join(data_path, "annotation_FSC147_384.json"))
+        self.data_split = _load_json(os.path.join(data_path, "Train_Test_Val_FSC_147.json"))[split]
+
+    def __len__(self):
+        return len(self.data_split)
+
+    def __getitem__(self, idx):
+        im_id = self.data_split[idx]
+        centres, whs = _exemplar_centres_whs(self.annotations[im_id])
+        image = Image.open(os.path.join(self.im_dir, im_id))
+        img_w, img_h = image.size
+        image = image.resize((32 * int(img_w / 32), 32 * int(img_h / 32)), Image.BILINEAR)
+        res = np.array([img_w, img_h], dtype=np.float32)
+        return {"image": to_normalized_tensor(image), "points": centres / res[None, :], "whs": whs / res[None, :],
+                "labels": np.zeros(centres.shape[0], dtype=np.int64), "orig_size": np.array([img_w, img_h])}
+
+
+class FSC147PointsDataset(Dataset):
+    """Pseudo-label reader (A1/datasets/fscd_147.py:76-136, FSCD147_Points): every annotated dot of an image (normalised by the original
+    size), the exemplar centres as `anchor_points`, orig_size = (width, height) and the numeric image id -- what
+    stage1.write_pseudo_labels consumes.  Image resized to a multiple of `scale_factor` with BILINEAR."""
+
+    def __init__(self, args, split="train"):
+        data_path = args.data_path
+        self.im_dir = os.path.join(data_path, "images_384_VarV2")
+        self.scale_factor = getattr(args, "scale_factor", 32)
+        self.annotations = _load_json(os.path.join(data_path, "annotation_FSC147_384.json"))
+        self.data_split = _load_json(os.path.join(data_path, "Train_Test_Val_FSC_147.json"))[split]
+
+    def __len__(self):
+        return len(self.data_split)
+
+    def __getitem__(self, idx):
+        im_id = self.data_split[idx]
+        anno = self.annotations[im_id]
+        all_points = np.array(anno["points"], dtype=np.float32).reshape(-1, 2)
+        centres, _ = _exemplar_centres_whs(anno)
+        image = Image.open(os.path.join(self.im_dir, im_id))
+        img_w, img_h = image.size
+        res = np.array([img_w, img_h], dtype=np.float32)
+        sf = self.scale_factor
+        image = image.resize((sf * int(img_w / sf), sf * int(img_h / sf)), Image.BILINEAR)
+        return {"im_id": int(im_id[:-4]), "image": to_normalized_tensor(image), "points": all_points / res[None, :],
+                "labels": np.zeros(all_points.shape[0], dtype=np.int64), "anchor_points": centres / res[None, :],
+                "orig_size": np.array([img_w, img_h])}
+
+
+def collate_stage1(samples):
+    """List of 1st-stage samples -> batch dict: images padded to the batch maximum with the padding mask (as `collate`), points and whs
+    stacked to [B,N,2] (every image of a batch needs the same number N of exemplars / points: the step pairs query n with exemplar n),
+    orig_size [B,2]; im_id [B] when the samples carry it."""
+    B = len(samples)
+    counts = [np.asarray(s["points"]).reshape(-1, 2).shape[0] for s in samples]
+    if len(set(counts)) != 1:
+        raise ValueError(f"collate_stage1: the images of a batch hold different numbers of points {counts}; batch them by count "
+                         "(or use batch size 1, the reference's)")
+    Hm = max(s["image"].shape[1] for s in samples)
+    Wm = max(s["image"].shape[2] for s in samples)
+    image = torch.zeros((B, 3, Hm, Wm), dtype=torch.float32)
+    mask = torch.ones((B, Hm, Wm), dtype=torch.bool)
+    for b, s in enumerate(samples):
+        _, h, w = s["image"].shape
+        image[b, :, :h, :w] = s["image"]
+        mask[b, :h, :w] = False
+    out = {"image": image, "mask": mask,
+           "points": torch.stack([torch.as_tensor(s["points"], dtype=torch.float32).reshape(-1, 2) for s in samples]),
+           "orig_size": torch.as_tensor(np.stack([np.asarray(s["orig_size"]) for s in samples]))}
+    if "whs" in samples[0]:
+        out["whs"] = torch.stack([torch.as_tensor(s["whs"], dtype=torch.float32).reshape(-1, 2) for s in samples])
+    if "im_id" in samples[0]:
+        out["im_id"] = torch.as_tensor([int(s["im_id"]) for s in samples])
+    return out
+
+
+def build_dataset_stage1(args, image_set="train"):
+    return FSC147ExemplarDataset(args, split=image_set)
+
+
+def build_points_dataset(args, image_set="train"):
+    return FSC147PointsDataset(args, split=image_set)
+
+
 def build_dataset(args):
     if getattr(args, "dataset", "fsc147") == "fscd_lvis":
         return FSCDLVISDataset(args, split="train")

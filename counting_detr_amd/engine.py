@@ -305,6 +305,10 @@ def _scoped(fn):
 
 
 class Trainer:
+    # parameters the model builds but the loss never reaches: their gradient stays None in the reference, so the optimizer leaves them alone
+    # (torch's AdamW skips a parameter without a gradient, weight decay included) -- they are kept out of the flat arena
+    unused_prefixes = UNUSED_PREFIXES
+
     def __init__(self, model, criterion, args, device=None, precision=None, precision_bwd=None):
         """precision / precision_bwd: the matrix-core arithmetic this trainer computes in (ops.PRECISION / PRECISION_BWD codes); default:
         the module defaults at construction time.  Every step, capture and replay of the trainer runs under them (ops.arithmetic)."""
@@ -314,9 +318,9 @@ class Trainer:
         self.device = torch.device(device or args.device)
         self.max_norm = args.clip_max_norm
         self.betas, self.eps, self.wd = (0.9, 0.999), 1e-8, args.weight_decay
-        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and not n.startswith(UNUSED_PREFIXES)]
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and not n.startswith(self.unused_prefixes)]
         for n, p in model.named_parameters():
-            if n.startswith(UNUSED_PREFIXES):
+            if n.startswith(self.unused_prefixes):
                 p.grad = None
         named.sort(key=lambda np_: _segment_of(np_[0]))            # stable: keeps definition order inside a segment
         self.names = [n for n, _ in named]
@@ -598,15 +602,18 @@ class Trainer:
         if sc is not None:
             sc.__exit__(None, None, None)
 
+    def _call_model(self, images, mask, rects):
+        """The model call of a step -> the output dict (stage 2: AnchorDETR(samples, rects=...) -> (outputs, reference points))."""
+        outputs, _ = self.model(NestedTensor(images, mask), rects=rects)
+        return outputs
+
     def _forward(self, images, mask, rects):
         """Forward weight images + model forward.  Leaves ops.MIRROR armed: `_loss_backward` (or `_trunk_segment(last=True)`) disarms it."""
-        from .misc import NestedTensor
-        from . import ops
         if self.mirror is not None:
             self.mirror.refresh("fwd")
         self._arm_mirror()
         try:
-            outputs, _ = self.model(NestedTensor(images, mask), rects=rects)
+            outputs = self._call_model(images, mask, rects)
         except BaseException:
             self._disarm_mirror()
             raise
@@ -711,9 +718,8 @@ class Trainer:
     def _dry_run(self, st):
         """Forward + criterion without autograd: builds every lazily cached device table (frozen-BN folds, padded stem
         weight, match plans, LDS attributes) OUTSIDE the capture; parameters are untouched."""
-        from .misc import NestedTensor
         with torch.no_grad():
-            outputs, _ = self.model(NestedTensor(st["images"], st["mask"]), rects=st["rects"])
+            outputs = self._call_model(st["images"], st["mask"], st["rects"])
             self.criterion(outputs, st["targets"], num_boxes=1.0)
 
     def _queries(self):
@@ -742,6 +748,11 @@ class Trainer:
               "num_boxes": torch.ones(1, device=self.device, dtype=torch.float32)}
         self._load_num_boxes(st, targets)
         return st
+
+    @staticmethod
+    def batch_args(ret):
+        """(rects, targets) of a data-loader sample dict: the arguments `step` takes after the images."""
+        return ret["ex_rects"], ret["targets"]
 
     def _load_num_boxes(self, st, targets):
         nb = self._num_boxes(targets)
@@ -937,7 +948,8 @@ class Trainer:
         from . import ops
         _ = self.mirror                            # (re)built OUTSIDE any capture: its tables are uploaded with synchronous copies
         st = self._make_static(images, mask, rects, targets)
-        st["sizes"] = tuple(len(t["boxes"]) for t in targets)
+        if "sizes" not in st:
+            st["sizes"] = tuple(len(t["boxes"]) for t in targets)
         world = get_world_size()
         hook = _bb._BACKWARD_HOOK
         _bb.set_backward_hook(None)                # no collectives inside the capture
@@ -1404,6 +1416,11 @@ class Trainer:
         return self._replay_entry(e, token, next_samples)
 
     # ------------------------------------------------------------------ graph cache: the step the data loader drives
+    def _cache_key(self, images, rects, targets):
+        """Key of a captured step in the graph cache: (padded image shape, exemplar shape, target-capacity class) + arithmetic."""
+        cap = self.target_capacity(max([len(t["boxes"]) for t in targets], default=0))
+        return (tuple(images.shape), tuple(rects.shape), cap) + self.arith
+
     @_scoped
     def step(self, samples, rects, targets, next_samples=None):
         """One training step on an arbitrary batch at graph-replay speed: captured steps are cached by (padded image size, batch,
@@ -1419,11 +1436,10 @@ class Trainer:
         from . import ops
         if not self._cache_on or not self.flat_g.is_cuda or not self.counts_on_device():
             # (a criterion that reads the counts on the host would replay the captured batch's matching layout: stream-ordered step)
-            return self.train_step(samples, rects, targets)
+            return Trainer.train_step(self, samples, rects, targets)
         nt = samples if hasattr(samples, "decompose") else nested_tensor_from_tensor_list(samples)
         images, mask = nt.decompose()
-        cap = self.target_capacity(max([len(t["boxes"]) for t in targets], default=0))
-        key = (tuple(images.shape), tuple(rects.shape), cap) + self.arith
+        key = self._cache_key(images, rects, targets)
         e = self._cache.pop(key, None)
         token = self._token(samples)
         if e is None:
@@ -1449,6 +1465,99 @@ class Trainer:
         self._cache[key] = e                       # most recently used last
         self.cache_stats["steps"] += 1
         return self._replay_entry(e, token, next_samples)
+
+
+class Stage1Trainer(Trainer):
+    """The 1st-stage step (A1/engine.py:26-85, A1/main.py:164-204) on the same machinery as `Trainer`: flat-arena clip + AdamW, the
+    stream-ordered `train_step` and the graph-captured `step` (linear graphs only, the chain layout).  Only the stage-specific hooks
+    differ: the model call `model(samples, points)`, the fused BoundingBoxCriterion (ops.BBoxCriterionFn; no matcher, no loss
+    normaliser to all-reduce), static buffers for (images, mask, points, whs), and captured steps keyed by (padded image shape,
+    points shape, arithmetic).  `transformer.cls_embed.*` is computed but never reaches the loss: its gradient is None in the
+    reference, so it stays out of the optimizer (as do the frozen stem and layer1).
+    Out of scope: world_size > 1 (raises), --sgd (raises); the frozen-stage prefetch is off."""
+
+    unused_prefixes = ("transformer.cls_embed.",)
+
+    def __init__(self, model, criterion, args, device=None, precision=None, precision_bwd=None):
+        if get_world_size() > 1:
+            raise NotImplementedError("Stage1Trainer: world_size > 1 is not supported (the 1st stage trains on one GPU)")
+        if getattr(args, "sgd", False):
+            raise NotImplementedError("Stage1Trainer: --sgd is not supported (A1's default optimizer, AdamW, is)")
+        pattern = getattr(getattr(model, "transformer", None), "num_pattern", 1)
+        if int(pattern) != 1:
+            raise ValueError(f"Stage1Trainer: num_query_pattern must be 1 (got {pattern}): query n is paired with exemplar n")
+        criterion.fused = True
+        super().__init__(model, criterion, args, device=device, precision=precision, precision_bwd=precision_bwd)
+        self._prefetch_on = False
+
+    @staticmethod
+    def batch_args(ret):
+        return ret["points"], ret["whs"]
+
+    @staticmethod
+    def _targets(points, whs):
+        return {"points": points, "whs": whs}
+
+    def _call_model(self, images, mask, rects):
+        return self.model(NestedTensor(images, mask), rects)
+
+    def _criterion_forward(self, outputs, targets, num_boxes):
+        return self.criterion.forward_with_total(outputs, targets)
+
+    def _num_boxes(self, targets):
+        return 1.0                              # (A1's criterion averages over its own pairs: nothing to normalise across ranks)
+
+    def counts_on_device(self):
+        return True                             # (no counts: the points shape is part of the cache key)
+
+    def target_capacity(self, tmax):
+        return int(tmax)
+
+    def _cache_key(self, images, rects, targets):
+        return (tuple(images.shape), tuple(rects.shape)) + self.arith
+
+    def _dry_run(self, st):
+        with torch.no_grad():
+            outputs = self._call_model(st["images"], st["mask"], st["rects"])
+            self.criterion.forward_with_total(outputs, st["targets"])
+
+    def _make_static(self, images, mask, rects, targets):
+        pts = rects.to(torch.float32).clone()
+        whs = targets["whs"].to(torch.float32).clone()
+        if tuple(whs.shape) != tuple(pts.shape):
+            raise ValueError(f"points {tuple(pts.shape)} and whs {tuple(whs.shape)} differ in shape")
+        return {"images": images.clone(), "mask": mask.clone(), "rects": pts, "whs": whs, "targets": self._targets(pts, whs),
+                "num_boxes": torch.ones(1, device=self.device, dtype=torch.float32), "sizes": tuple(pts.shape)}
+
+    def _load_entry(self, e, images, mask, rects, targets):
+        st = e["st"]
+        if tuple(rects.shape) != tuple(st["rects"].shape) or tuple(images.shape) != tuple(st["images"].shape) \
+                or tuple(targets["whs"].shape) != tuple(st["whs"].shape):
+            raise ValueError(f"captured step holds images {tuple(st['images'].shape)} / points {tuple(st['rects'].shape)}, "
+                             f"got {tuple(images.shape)} / {tuple(rects.shape)} / whs {tuple(targets['whs'].shape)}")
+        st["images"].copy_(images)
+        st["mask"].copy_(mask)
+        st["rects"].copy_(rects)
+        st["whs"].copy_(targets["whs"])
+        e["loads"] += 1
+
+    # public entry points: (samples, points [B,N,2], whs [B,N,2]) instead of (samples, rects, targets)
+    def train_step(self, samples, points, whs):
+        """Eager (stream-ordered) step.  samples: [B,3,H,W] tensor, list of [3,h,w] tensors, or NestedTensor; points / whs [B,N,2]
+        normalised (exemplar centres and sizes).  Returns device scalars {loss_wh, loss_giou, loss, grad_norm}."""
+        return Trainer.train_step(self, samples, points, self._targets(points, whs))
+
+    def step(self, samples, points, whs, next_samples=None):
+        """One step at graph-replay speed: captured steps are cached by (padded image shape, points shape, arithmetic); a batch of a
+        cached key is copied into the static buffers and replayed.  Returns the loss dict (device scalars, valid until the same entry
+        is replayed again)."""
+        return Trainer.step(self, samples, points, self._targets(points, whs))
+
+    def capture(self, samples, points, whs, warmup=0):
+        return Trainer.capture(self, samples, points, self._targets(points, whs), warmup)
+
+    def replay(self, samples=None, points=None, whs=None):
+        return Trainer.replay(self, samples, points, None if whs is None else self._targets(points, whs))
 
 
 def train_one_epoch(trainer, data_loader, epoch, print_freq=100, log=print):
@@ -1486,7 +1595,8 @@ def train_one_epoch(trainer, data_loader, epoch, print_freq=100, log=print):
         samples = NestedTensor(ret["image"], ret["mask"]) if "mask" in ret else ret["image"]     # data.collate pads + masks
         nxt_img = nxt["image"] if (nxt is not None and torch.is_tensor(nxt.get("image"))) else None
         # cached HIP graph per padded size / target-capacity class; the next batch's image tensor is announced (frozen-stage prefetch)
-        out = trainer.step(samples, ret["ex_rects"], ret["targets"], next_samples=nxt_img)
+        batch_args = getattr(trainer, "batch_args", Trainer.batch_args)
+        out = trainer.step(samples, *batch_args(ret), next_samples=nxt_img)
         if keys is None:
             keys = sorted(k for k, v in out.items() if torch.is_tensor(v))
             acc = torch.zeros(len(keys), device=trainer.device, dtype=torch.float32)

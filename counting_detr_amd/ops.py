@@ -1930,6 +1930,46 @@ class CriterionFn(torch.autograd.Function):
         return (d_logits, d_boxes, d_vars) + (None,) * 9
 
 
+class BBoxCriterionFn(torch.autograd.Function):
+    """The 1st-stage BoundingBoxCriterion (A1/models/anchor_detr.py:317-337) in one launch (cdetr_bbox_criterion_fwd): returns
+    vec = [loss_wh, loss_giou, w_wh * loss_wh + w_giou * loss_giou].  `coord` is the box head's [B,N,4] output (cxcywh); its wh
+    columns are read in place (pointer + row stride, no copy) and its xy columns take no part (stage 1 builds both boxes around the
+    GIVEN points).  tgt_points / tgt_whs [B,N,2].  The forward leaves the gradient of both losses w.r.t. pred_wh; backward is one
+    scaled sum (cdetr_bbox_criterion_bwd) into d_coord [B,N,4] with zeros in the xy columns."""
+
+    @staticmethod
+    def forward(ctx, coord, tgt_points, tgt_whs, w_wh, w_giou):
+        if coord.dim() != 3 or coord.shape[-1] != 4 or coord.dtype != torch.float32:
+            raise ValueError(f"BBoxCriterionFn: coord must be float32 [B,N,4], got {tuple(coord.shape)} {coord.dtype}")
+        B, N, _ = coord.shape
+        if tuple(tgt_whs.shape) != (B, N, 2) or tuple(tgt_points.shape) != (B, N, 2):
+            # (the reference fails here too: with num_query_pattern != 1 the model predicts N * patterns boxes for N targets)
+            raise ValueError(f"BBoxCriterionFn: {B}x{N} predicted boxes, targets {tuple(tgt_points.shape)} points / "
+                             f"{tuple(tgt_whs.shape)} sizes (stage 1 pairs query n with exemplar n: num_query_pattern must be 1)")
+        if coord.stride(2) != 1 or coord.stride(0) != N * coord.stride(1):
+            coord = coord.contiguous()
+        tp = tgt_points.to(torch.float32).contiguous()
+        tw = tgt_whs.to(torch.float32).contiguous()
+        M = B * N
+        dev = coord.device
+        losses = torch.empty(3, device=dev, dtype=torch.float32)
+        g = torch.empty(4 * M, device=dev, dtype=torch.float32)
+        g_wh, g_giou = g[:2 * M], g[2 * M:]
+        check(lib().cdetr_bbox_criterion_fwd(ptr(coord) + 8, coord.stride(1), ptr(tp), ptr(tw), M, float(w_wh), float(w_giou),
+                                             ptr(losses), ptr(g_wh), ptr(g_giou), stream_ptr()), "cdetr_bbox_criterion_fwd")
+        ctx.g, ctx.dims, ctx.w = (g_wh, g_giou), (B, N), (float(w_wh), float(w_giou))
+        return losses
+
+    @staticmethod
+    def backward(ctx, g3):
+        B, N = ctx.dims
+        g_wh, g_giou = ctx.g
+        d_coord = torch.empty((B, N, 4), device=g_wh.device, dtype=torch.float32)
+        check(lib().cdetr_bbox_criterion_bwd(ptr(g3.contiguous()), ctx.w[0], ctx.w[1], ptr(g_wh), ptr(g_giou), ptr(d_coord), B * N,
+                                             stream_ptr()), "cdetr_bbox_criterion_bwd")
+        return d_coord, None, None, None, None
+
+
 class SineEmbedFn(torch.autograd.Function):
     """pos2posemb1d / pos2posemb2d (A2/models/transformer.py:474-494) in one launch per coordinate.
     pos [..., ncoord] (ncoord 1 or 2); two coordinates give the reference's (y, x) concatenation of two nfeat-wide halves."""

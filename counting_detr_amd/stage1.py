@@ -3,7 +3,9 @@
 API mirror of A1/models/anchor_detr.py (A1 = src/CountDETR_147_1st_stage): `build(args) -> (model, criterion,
 postprocessors)`, `model(samples, scaled_sample_points) -> {"pred_logits", "pred_wh", "pred_points"}` (:80-113),
 `BoundingBoxCriterion` (:317-337: L1 on wh + mean(1 - GIoU) of boxes built from the GT points and the predicted wh; no
-Hungarian matcher is involved in stage 1).  Differences to stage 2 (A1/models/transformer.py:60-214): the query embedding is
+Hungarian matcher is involved in stage 1; `fused = True` computes it in one launch, ops.BBoxCriterionFn).  The model's output also
+carries "pred_boxes" = the box head's [B,Q,4] output that "pred_points" / "pred_wh" are column views of (the fused criterion reads
+the wh columns in place).  Differences to stage 2 (A1/models/transformer.py:60-214): the query embedding is
 called `modify_pattern`, there is no variance head, the class bias has ONE element broadcast over 2 logits, the anchor
 points are `defined` = the given points (Q = number of points), the backbone output goes through `input_proj` (no
 exemplar aggregation).  State dict is key-compatible with the reference's stage-1 model.
@@ -12,7 +14,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import box_ops
+from . import box_ops, ops
 from .anchor_detr import PostProcess, _ProjGN
 from .backbone import BackboneAgg
 from .misc import NestedTensor, nested_tensor_from_tensor_list
@@ -33,20 +35,38 @@ class AnchorDETRStage1(nn.Module):
             samples = nested_tensor_from_tensor_list(samples)
         images, mask = samples.decompose()
         x = self.backbone.body.forward_nhwc(images)                          # NHWC [B,h,w,2048]
+        if ops.AFTER_BACKBONE is not None:                                   # (a trainer's schedule hook, as in AnchorDETR.forward)
+            ops.AFTER_BACKBONE()
         m = F.interpolate(mask[None].float(), size=x.shape[1:3]).to(torch.bool)[0]
         src = self.input_proj[0](x)
         (cls, xywh, _), _ = self.transformer(src, m, scaled_sample_points)
-        return {"pred_logits": cls[-1], "pred_wh": xywh[-1][..., 2:], "pred_points": xywh[-1][..., :2]}
+        return {"pred_logits": cls[-1], "pred_wh": xywh[-1][..., 2:], "pred_points": xywh[-1][..., :2], "pred_boxes": xywh[-1]}
 
 
 class BoundingBoxCriterion(nn.Module):
-    """A1/models/anchor_detr.py:317-337."""
+    """A1/models/anchor_detr.py:317-337.  `fused = False` (default): the reference's chain of tensor ops.  `fused = True`: one launch
+    (ops.BBoxCriterionFn over outputs["pred_boxes"]) that also forms the weighted total -- what engine.Stage1Trainer uses."""
 
-    def __init__(self):
+    def __init__(self, fused=False):
         super().__init__()
         self.weight_dict = {"loss_wh": 1, "loss_giou": 0.4}
+        self.fused = bool(fused)
 
     def forward(self, outputs, targets):
+        return self.forward_with_total(outputs, targets)[0]
+
+    def forward_with_total(self, outputs, targets):
+        """(loss dict, weighted total sum_k loss_k * weight_dict[k]) -- A1/engine.py's `losses`."""
+        wd = self.weight_dict
+        if self.fused:
+            if "pred_boxes" not in outputs:
+                raise KeyError("the fused BoundingBoxCriterion reads the box head's [B,Q,4] output: outputs['pred_boxes'] is missing")
+            vec = ops.BBoxCriterionFn.apply(outputs["pred_boxes"], targets["points"], targets["whs"], wd["loss_wh"], wd["loss_giou"])
+            return {"loss_wh": vec[0], "loss_giou": vec[1]}, vec[2]
+        loss_dict = self._composition(outputs, targets)
+        return loss_dict, sum(loss_dict[k] * wd[k] for k in loss_dict if k in wd)
+
+    def _composition(self, outputs, targets):
         tgt_points = targets["points"].flatten(0, 1)
         src_whs = outputs["pred_wh"].flatten(0, 1)
         tgt_whs = targets["whs"].flatten(0, 1)

@@ -294,7 +294,12 @@ class Transformer(nn.Module):
             return ref.unsqueeze(0).repeat(bs, self.num_pattern, 1)
         if self.spatial_prior == "defined":
             assert points is not None, "defined, provide points"
-            pts = torch.as_tensor(points, dtype=torch.float32, device=device).reshape(-1, 2)
+            pts = torch.as_tensor(points, dtype=torch.float32, device=device)
+            if bs > 1 and pts.dim() == 3 and pts.shape[0] == bs:
+                # batched extension (the reference runs batch 1: points.squeeze(0)): image b's queries sit at ITS OWN points [B,N,2]
+                self.num_position = pts.shape[1]
+                return pts.repeat(1, self.num_pattern, 1)
+            pts = pts.reshape(-1, 2)
             self.num_position = pts.shape[0]
             return pts.unsqueeze(0).repeat(bs, self.num_pattern, 1)
         raise ValueError(f"unknown {self.spatial_prior} spatial prior")

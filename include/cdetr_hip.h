@@ -1,7 +1,8 @@
 /* cdetr_hip.h -- C-ABI of libcdetr_hip.so: the MI355X (gfx950) kernels of the Counting-DETR hot path.
  *
  * The reference (VinAIResearch/Counting-DETR) is pure Python/PyTorch and has NO FFI of its own; each entry
- * point below replaces the torch-op sequence at the cited reference lines (A2/ = src/CountDETR_147_2nd_stage/).
+ * point below replaces the torch-op sequence at the cited reference lines (A2/ = src/CountDETR_147_2nd_stage/,
+ * A1/ = src/CountDETR_147_1st_stage/: cdetr_bbox_criterion_fwd / _bwd, the 1st stage's BoundingBoxCriterion).
  * INTEGRATION.md shows the ctypes stub a reference maintainer would add at each site.
  *
  * Conventions
@@ -411,6 +412,21 @@ int cdetr_criterion_fwd(const cdetr_criterion_desc* d, void* stream);
 int cdetr_criterion_bwd(const float* g6, const float* g_total, const float* loss_weights, const float* g_logits, const float* g_l1,
                         const float* g_giou, const float* g_var_box, const float* g_vars, float* d_logits, float* d_boxes, float* d_vars,
                         int32_t BQ, int32_t C, void* stream);
+
+/* ---- 1st-stage BoundingBoxCriterion (A1/models/anchor_detr.py:317-337; no matcher: query n of image b <-> exemplar n) --------------
+ * cdetr_bbox_criterion_fwd: M = B*N pairs, src = [tgt_points, pred_wh], tgt = [tgt_points, tgt_whs] (cxcywh):
+ *   losses[3] = { loss_wh = mean |pred_wh - tgt_whs| (2M elements), loss_giou = sum (1 - GIoU(src, tgt)) / M,
+ *                 total = w_wh * loss_wh + w_giou * loss_giou }
+ * and the per-element gradients g_wh / g_giou [M,2] = d {loss_wh, loss_giou} / d pred_wh (torch's subgradients: sign(0) = 0, equal
+ * operands of max / min split the gradient evenly, clamp(min=0) passes it at 0).  pred_wh is read IN PLACE: row r's (w, h) are
+ * pred_wh[r * pred_stride + {0, 1}] (the [..., 2:] columns of the box head's [B,Q,4] output: pointer + 2 floats, stride 4).
+ * tgt_points / tgt_whs are contiguous [M,2].  One workgroup, ordered reductions: bit-reproducible for any M >= 1.
+ * cdetr_bbox_criterion_bwd: d_coord [M,4] (16-byte aligned) = (0, 0, e_wh g_wh + e_giou g_giou) with e_k = g3[k] + g3[2] w_k
+ * (g3 = upstream gradient of the three scalars, device).                                                                   */
+int cdetr_bbox_criterion_fwd(const float* pred_wh, int64_t pred_stride, const float* tgt_points, const float* tgt_whs, int32_t M,
+                             float w_wh, float w_giou, float* losses, float* g_wh, float* g_giou, void* stream);
+int cdetr_bbox_criterion_bwd(const float* g3, float w_wh, float w_giou, const float* g_wh, const float* g_giou, float* d_coord,
+                             int32_t M, void* stream);
 
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);

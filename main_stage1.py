@@ -1,0 +1,153 @@
+"""main_stage1.py -- CLI of the reference's 1st-stage trainer (A1/main.py, A1 = src/CountDETR_147_1st_stage) on the MI355X path.
+
+Same flags, same driver: stage1.build -> three lr groups / AdamW / StepLR(lr_drop) + clip 0.1 (engine.Stage1Trainer) -> optional --resume
+(model weights, `transformer.pattern.weight` filtered, so the COCO Anchor-DETR checkpoint loads) -> per epoch train_one_epoch, scheduler
+step, checkpoint {"model","optimizer","lr_scheduler","epoch","args"} to <output_dir>/checkpoint.pth (+ checkpoint<epoch:04>.pth at lr_drop
+and every 10 epochs), one JSON line per epoch in log.txt.
+  --eval                   validation loss (A1/engine.py evaluate) of the model, then exit (A1's own --eval then unpacks a COCO evaluator
+                           that evaluate never returns and crashes: not reproduced)
+  --generate_pseudo_label  load --resume and write pseudo_bbox_{train,val,test}.json (the 2nd stage's training labels), then exit
+  --auto_resume            continue from <output_dir>/checkpoint.pth: weights, AdamW moments, StepLR state and the next epoch
+  --synthetic              seeded batches, no dataset
+Differences: any number of images per step with equal exemplar counts (--batch_size; the reference trains batch 1), and the step runs
+as cached HIP graphs (--no_graph_cache: stream-ordered).  --sgd and multi-GPU training are not supported.
+
+  python main_stage1.py --data_path ./FSC147/ --output_dir ./outputs/fscd_147_1st_stage --resume ./pretrained_models/AnchorDETR_r50_c5.pth
+  python main_stage1.py --data_path ./FSC147/ --output_dir ./outputs/fscd_147_1st_stage --dataset_file fscd_147_point \\
+      --generate_pseudo_label --resume ./outputs/fscd_147_1st_stage/checkpoint.pth
+"""
+import json
+import os
+import time
+from pathlib import Path
+
+import torch
+
+from counting_detr_amd import checkpoint as ckpt_io
+from counting_detr_amd import stage1
+from counting_detr_amd.args import get_args_parser_stage1
+from counting_detr_amd.engine import Stage1Trainer, train_one_epoch
+
+
+class SyntheticLoader:
+    """Seeded stand-in for FSC147ExemplarDataset + DataLoader: yields the step's batch dict (on the device)."""
+
+    def __init__(self, args, device, steps, size=(384, 576), npts=3):
+        self.args, self.device, self.steps, self.size, self.npts = args, device, steps, size, npts
+
+    def __iter__(self):
+        B = self.args.batch_size
+        H, W = self.size
+        for it in range(self.steps):
+            g = torch.Generator().manual_seed(1000003 + it)
+            yield {"image": torch.randn(B, 3, H, W, generator=g).to(self.device),
+                   "points": (torch.rand(B, self.npts, 2, generator=g) * 0.6 + 0.2).to(self.device),
+                   "whs": (torch.rand(B, self.npts, 2, generator=g) * 0.15 + 0.03).to(self.device)}
+
+    def __len__(self):
+        return self.steps
+
+
+def to_device(loader, device):
+    for b in loader:
+        yield {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in b.items()}
+
+
+def loader_for(args, split, points=False, shuffle=False):
+    from torch.utils.data import DataLoader
+    from counting_detr_amd import data
+    ds = data.build_points_dataset(args, split) if points else data.build_dataset_stage1(args, split)
+    return DataLoader(ds, batch_size=1 if points else args.batch_size, shuffle=shuffle, collate_fn=data.collate_stage1,
+                      num_workers=args.num_workers, drop_last=shuffle)
+
+
+@torch.no_grad()
+def evaluate(model, criterion, loader, device):
+    """A1/engine.py evaluate: mean over the batches of the validation losses (loss = weighted total, loss_wh, loss_giou)."""
+    from counting_detr_amd.misc import NestedTensor
+    model.eval()
+    acc, n = None, 0
+    for ret in to_device(loader, device):
+        out = model(NestedTensor(ret["image"], ret["mask"]), ret["points"])
+        ld, total = criterion.forward_with_total(out, {"points": ret["points"], "whs": ret["whs"]})
+        v = torch.stack([total, ld["loss_wh"], ld["loss_giou"]])
+        acc = v if acc is None else acc + v
+        n += 1
+    model.train()
+    if n == 0:
+        return {}
+    acc = (acc / n).tolist()
+    return {"loss": acc[0], "loss_wh": acc[1], "loss_giou": acc[2], "batches": n}
+
+
+def main(args):
+    device = torch.device(args.device)
+    torch.manual_seed(args.seed)
+    model, criterion, _ = stage1.build(args)
+    model.to(device)
+    criterion.fused = True                     # one launch (ops.BBoxCriterionFn); the validation loss goes through it as well
+    output_dir = Path(args.output_dir)
+    os.makedirs(output_dir, exist_ok=True)
+    if args.auto_resume:                       # A1/main.py:218-222
+        if not args.resume:
+            args.resume = str(output_dir / "checkpoint.pth")
+        if not os.path.isfile(args.resume):
+            args.resume = ""
+
+    if args.generate_pseudo_label:             # A1/main.py:247-272: the checkpoint as it is (strict=False), then the three splits
+        ckpt = ckpt_io._read(args.resume)
+        missing, unexpected = model.load_state_dict(ckpt["model"] if "model" in ckpt else ckpt, strict=False)
+        ckpt_io.invalidate_caches(model)
+        if missing:
+            print("Missing Keys: {}".format(missing))
+        if unexpected:
+            print("Unexpected Keys: {}".format(unexpected))
+        for split in ("train", "val", "test"):
+            ann = stage1.write_pseudo_labels(model, loader_for(args, split, points=True), split, args.output_dir, device=device)
+            print(f"pseudo_bbox_{split}.json: {len(ann['images'])} images, {len(ann['annotations'])} boxes")
+        return
+
+    checkpoint = None
+    if args.resume:                            # A1/main.py:224-239 (weights; transformer.pattern.weight filtered)
+        checkpoint, _, _ = ckpt_io.resume_model(model, args.resume)
+
+    if args.eval:
+        stats = evaluate(model, criterion, loader_for(args, "val"), device)
+        print("validation:", json.dumps(stats))
+        return
+
+    trainer = Stage1Trainer(model, criterion, args, device=device)
+    if checkpoint is not None and args.auto_resume and checkpoint.get("optimizer"):
+        trainer.load_state_dict(checkpoint["optimizer"], checkpoint.get("lr_scheduler"))
+        resumed = int(checkpoint.get("epoch", -1)) + 1
+        if resumed > args.start_epoch:
+            print(f"resume: optimizer state restored, continuing at epoch {resumed}")
+            args.start_epoch = resumed
+    torch.manual_seed(args.seed + 1)
+    n_parameters = sum(p.numel() for p in model.parameters() if p.requires_grad)
+    print("Start training")
+    start = time.time()
+    for epoch in range(args.start_epoch, args.epochs):
+        if args.synthetic:
+            loader = SyntheticLoader(args, device, args.steps_per_epoch, size=tuple(args.synthetic_size))
+        else:
+            loader = to_device(loader_for(args, "train", shuffle=True), device)
+        stats = train_one_epoch(trainer, loader, epoch, print_freq=args.print_freq)
+        trainer.lr_scheduler_step()
+        paths = [output_dir / "checkpoint.pth"]
+        if (epoch + 1) % args.lr_drop == 0 or (epoch + 1) % 10 == 0:
+            paths.append(output_dir / f"checkpoint{epoch:04}.pth")
+        ckpt = {"model": model.state_dict(), "optimizer": trainer.state_dict(), "lr_scheduler": trainer.lr_scheduler_state_dict(),
+                "epoch": epoch, "args": args}
+        for p in paths:
+            torch.save(ckpt, p)
+        with (output_dir / "log.txt").open("a") as f:
+            f.write(json.dumps({**{f"train_{k}": v for k, v in stats.items()}, "epoch": epoch, "n_parameters": n_parameters}) + "\n")
+    print("Training time {:.1f} s".format(time.time() - start))
+
+
+if __name__ == "__main__":
+    a = get_args_parser_stage1().parse_args()
+    if a.output_dir:
+        Path(a.output_dir).mkdir(parents=True, exist_ok=True)
+    main(a)
