@@ -54,6 +54,13 @@ class RcdaBwdDesc(C.Structure):
                 ("q_row", _p), ("q_col", _p), ("dk_row", _p), ("dk_col", _p)]
 
 
+class AttnDesc(C.Structure):
+    _fields_ = [("q", _p), ("k", _p), ("v", _p), ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("o", _p), ("lse", _p),
+                ("d_o", _p), ("d_q", _p), ("d_k", _p), ("d_v", _p), ("ld_dq", C.c_int64), ("ld_dk", C.c_int64), ("ld_dv", C.c_int64),
+                ("work", _p), ("N", C.c_int32), ("Lq", C.c_int32), ("Lk", C.c_int32), ("nh", C.c_int32), ("scale", C.c_float),
+                ("precision", C.c_int32)]
+
+
 class CriterionDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("Q", C.c_int32), ("C", C.c_int32), ("num_classes", C.c_int32), ("Mmax", C.c_int32), ("alpha", C.c_float),
                 ("logits", _p), ("boxes", _p), ("vars", _p), ("tgt_boxes", _p), ("tgt_labels", _p), ("tgt_off", _p), ("idx_i", _p),
@@ -67,7 +74,7 @@ class MirrorItem(C.Structure):
 
 
 EXPORTS = ["cdetr_gemm", "cdetr_gemm_dl", "cdetr_gemm_group", "cdetr_wgrad", "cdetr_wgrad_group", "cdetr_colsum", "cdetr_sumsq", "cdetr_adamw_step", "cdetr_adamw_step2", "cdetr_relu_mask", "cdetr_relu_mask2", "cdetr_layernorm_fwd", "cdetr_layernorm_fwd_add", "cdetr_layernorm_bwd", "cdetr_layernorm_bwd_merge", "cdetr_groupnorm_fwd", "cdetr_groupnorm_bwd", "cdetr_groupnorm_fwd_ws", "cdetr_groupnorm_bwd_ws", "cdetr_posadd2",
-           "cdetr_hw_reduce", "cdetr_posadd2_hw_reduce", "cdetr_bcast_add2", "cdetr_bcast_add2_sum", "cdetr_add2", "cdetr_grad_merge", "cdetr_sine_embed", "cdetr_sine_embed_bwd", "cdetr_maxpool3x3s2", "cdetr_maxpool3x3s2_split", "cdetr_weight_mirror", "cdetr_weight_images", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_mha_fwd", "cdetr_mha_bwd",
+           "cdetr_hw_reduce", "cdetr_posadd2_hw_reduce", "cdetr_bcast_add2", "cdetr_bcast_add2_sum", "cdetr_add2", "cdetr_grad_merge", "cdetr_sine_embed", "cdetr_sine_embed_bwd", "cdetr_maxpool3x3s2", "cdetr_maxpool3x3s2_split", "cdetr_weight_mirror", "cdetr_weight_images", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_mha_fwd", "cdetr_mha_bwd", "cdetr_attn_fwd", "cdetr_attn_bwd",
            "cdetr_mask_prep", "cdetr_stem_pack", "cdetr_exemplar_fwd", "cdetr_exemplar_bwd", "cdetr_aggr_weight_fwd", "cdetr_aggr_weight_bwd",
            "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
 
@@ -86,7 +93,7 @@ def lib():
         L.cdetr_abi_version.restype = C.c_int
         L.cdetr_gemm_dl.restype = C.c_int
         L.cdetr_gemm_dl.argtypes = [_p, C.c_int32, C.c_int32, _p]
-        for name in ("cdetr_gemm", "cdetr_wgrad", "cdetr_rcda_fwd", "cdetr_rcda_bwd"):
+        for name in ("cdetr_gemm", "cdetr_wgrad", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_attn_fwd", "cdetr_attn_bwd"):
             getattr(L, name).restype = C.c_int
             getattr(L, name).argtypes = [_p, _p]
         L.cdetr_delay.restype = C.c_int

@@ -9,6 +9,12 @@
 //   mha_bwd_kv_kernel: dk, dv (lanes own keys, loop over query tiles) -- no atomics, P recomputed from the saved LSE.
 // fp32 VALU throughout (the matrix cores would not be fed by 32-wide heads at this size).
 // Layouts: qk [N][L][2E] (q | k), v [N][L][E], o / dO [N][L][E], lse / D [N][nh][L]; E = nh * 32.
+//
+// Every kernel body is written for the general problem (cdetr_attn_*): q [N][Lq] rows of stride ldq, k / v [N][Lk] rows of strides ldk / ldv
+// (head h at columns 32h .. 32h + 31 of a row; image n's rows start at n * L * ld), o / dO [N][Lq][E], lse / D [N][nh][Lq], gradients with
+// their own row strides.  cdetr_mha_* is the instance q = qk, k = qk + E (ldq = ldk = 2E), Lq = Lk = L: the same arithmetic, addresses only
+// computed differently.  The encoder's self-attention over h*w tokens and the decoder's cross-attention from Q queries to h*w keys of the
+// nn.MultiheadAttention variant (A2/models/transformer.py:262-272,393-398) run on the same kernels.
 #include "../../include/cdetr_hip.h"
 #include "common.h"
 #include <stdlib.h>
@@ -54,9 +60,9 @@ __device__ __forceinline__ void load_tile(float* __restrict__ dst, const float* 
     }
 }
 
-__global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ qk, const float* __restrict__ v,
-                                                      float* __restrict__ o, float* __restrict__ lse, int N, int L, int nh,
-                                                      float scale) {
+__global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                      const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
+                                                      int Lq, int Lk, int nh, float scale) {
     __shared__ __attribute__((aligned(16))) float Ks[KT * D];
     __shared__ __attribute__((aligned(16))) float Vs[KT * D];
     const int E = nh * D;
@@ -64,12 +70,13 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ 
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 64 + wid * 16 + i32;
-    const bool qv = q < L;
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* vn = v + (long)n * L * E;
+    const bool qv = q < Lq;
+    const float* qn = qg + (long)n * Lq * ldq;
+    const float* kn = kg + (long)n * Lk * ldk;
+    const float* vn = vg + (long)n * Lk * ldv;
     float qr[D];
     {
-        const float* qp = qkn + (long)(qv ? q : 0) * 2 * E + head * D;
+        const float* qp = qn + (long)(qv ? q : 0) * ldq + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 8; ++c4) {
             const float4 t = ld4(qp + c4 * 4);
@@ -79,12 +86,12 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ 
     float m = -INFINITY, l = 0.f, acc[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] = 0.f;
-    for (int k0 = 0; k0 < L; k0 += KT) {
+    for (int k0 = 0; k0 < Lk; k0 += KT) {
         __syncthreads();
-        load_tile(Ks, qkn, 2 * E, E + head * D, k0, L);
-        load_tile(Vs, vn, E, head * D, k0, L);
+        load_tile(Ks, kn, ldk, head * D, k0, Lk);
+        load_tile(Vs, vn, ldv, head * D, k0, Lk);
         __syncthreads();
-        const int nk = min(KT, L - k0);
+        const int nk = min(KT, Lk - k0);
         float s[KT / 4];
         float tm = -INFINITY;
 #pragma unroll
@@ -127,20 +134,20 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ 
         acc[c] = a * inv;
     }
     if (qv) {
-        float* op = o + ((long)n * L + q) * E + head * D + g * 8;      // each lane group writes 8 channels
+        float* op = o + ((long)n * Lq + q) * E + head * D + g * 8;     // each lane group writes 8 channels
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4)
             *reinterpret_cast<float4*>(op + c4 * 4) = make_float4(acc[g * 8 + c4 * 4 + 0], acc[g * 8 + c4 * 4 + 1],
                                                                   acc[g * 8 + c4 * 4 + 2], acc[g * 8 + c4 * 4 + 3]);
-        if (g == 0) lse[((long)n * nh + head) * L + q] = mn + logf(l);
+        if (g == 0) lse[((long)n * nh + head) * Lq + q] = mn + logf(l);
     }
 }
 
 // dq[i] = scale * sum_j p_ij (dO_i.v_j - D_i) k_j,   D_i = dO_i . O_i   (lanes own queries)
-__global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict__ qk, const float* __restrict__ v,
-                                                        const float* __restrict__ o, const float* __restrict__ dO,
-                                                        const float* __restrict__ lse, float* __restrict__ dqk,
-                                                        float* __restrict__ Dbuf, int N, int L, int nh, float scale) {
+__global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                        const float* __restrict__ vg, long ldv, const float* __restrict__ o,
+                                                        const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dq_out,
+                                                        long lddq, float* __restrict__ Dbuf, int Lq, int Lk, int nh, float scale) {
     __shared__ __attribute__((aligned(16))) float Ks[KT * D];
     __shared__ __attribute__((aligned(16))) float Vs[KT * D];
     const int E = nh * D;
@@ -148,14 +155,15 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 64 + wid * 16 + i32;
-    const bool qv = q < L;
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* vn = v + (long)n * L * E;
+    const bool qv = q < Lq;
+    const float* qn = qg + (long)n * Lq * ldq;
+    const float* kn = kg + (long)n * Lk * ldk;
+    const float* vn = vg + (long)n * Lk * ldv;
     float qr[D], dor[D], dq[D];
     float Di = 0.f;
     {
-        const long row = (long)n * L + (qv ? q : 0);
-        const float* qp = qkn + (long)(qv ? q : 0) * 2 * E + head * D;
+        const long row = (long)n * Lq + (qv ? q : 0);
+        const float* qp = qn + (long)(qv ? q : 0) * ldq + head * D;
         const float* dp = dO + row * E + head * D;
         const float* op = o + row * E + head * D;
 #pragma unroll
@@ -168,13 +176,13 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < D; ++c) dq[c] = 0.f;
     }
-    const float li = qv ? lse[((long)n * nh + head) * L + q] : 0.f;
-    for (int k0 = 0; k0 < L; k0 += KT) {
+    const float li = qv ? lse[((long)n * nh + head) * Lq + q] : 0.f;
+    for (int k0 = 0; k0 < Lk; k0 += KT) {
         __syncthreads();
-        load_tile(Ks, qkn, 2 * E, E + head * D, k0, L);
-        load_tile(Vs, vn, E, head * D, k0, L);
+        load_tile(Ks, kn, ldk, head * D, k0, Lk);
+        load_tile(Vs, vn, ldv, head * D, k0, Lk);
         __syncthreads();
-        const int nk = min(KT, L - k0);
+        const int nk = min(KT, Lk - k0);
         for (int kk = g; kk < nk; kk += 4) {
             const float p = expf(dot32(qr, Ks + kk * D) - li);
             const float ds = p * (dot32(dor, Vs + kk * D) - Di);
@@ -189,20 +197,21 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
         dq[c] = a * scale;
     }
     if (qv) {
-        float* out = dqk + ((long)n * L + q) * 2 * E + head * D;
+        float* out = dq_out + ((long)n * Lq + q) * lddq + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4)
             *reinterpret_cast<float4*>(out + g * 8 + c4 * 4) = make_float4(dq[g * 8 + c4 * 4 + 0], dq[g * 8 + c4 * 4 + 1],
                                                                            dq[g * 8 + c4 * 4 + 2], dq[g * 8 + c4 * 4 + 3]);
-        if (g == 0) Dbuf[((long)n * nh + head) * L + q] = Di;
+        if (g == 0) Dbuf[((long)n * nh + head) * Lq + q] = Di;
     }
 }
 
 // dk[j] = scale * sum_i p_ij (dO_i.v_j - D_i) q_i,   dv[j] = sum_i p_ij dO_i   (lanes own keys, query tiles through LDS)
-__global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict__ qk, const float* __restrict__ v,
-                                                         const float* __restrict__ dO, const float* __restrict__ lse,
-                                                         const float* __restrict__ Dbuf, float* __restrict__ dqk,
-                                                         float* __restrict__ dv, int N, int L, int nh, float scale) {
+__global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                         const float* __restrict__ vg, long ldv, const float* __restrict__ dO,
+                                                         const float* __restrict__ lse, const float* __restrict__ Dbuf,
+                                                         float* __restrict__ dk_out, long lddk, float* __restrict__ dv, long lddv,
+                                                         int Lq, int Lk, int nh, float scale) {
     __shared__ __attribute__((aligned(16))) float Qs[KT * D];
     __shared__ __attribute__((aligned(16))) float Os[KT * D];
     __shared__ float Ls[KT], Dsh[KT];
@@ -211,13 +220,13 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int j = blockIdx.x * 64 + wid * 16 + i32;
-    const bool jv = j < L;
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* don = dO + (long)n * L * E;
+    const bool jv = j < Lk;
+    const float* qn = qg + (long)n * Lq * ldq;
+    const float* don = dO + (long)n * Lq * E;
     float kr[D], vr[D], dk[D], dvv[D];
     {
-        const float* kp = qkn + (long)(jv ? j : 0) * 2 * E + E + head * D;
-        const float* vp = v + ((long)n * L + (jv ? j : 0)) * E + head * D;
+        const float* kp = kg + ((long)n * Lk + (jv ? j : 0)) * ldk + head * D;
+        const float* vp = vg + ((long)n * Lk + (jv ? j : 0)) * ldv + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 8; ++c4) {
             const float4 t = ld4(kp + c4 * 4), u = ld4(vp + c4 * 4);
@@ -227,17 +236,17 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
 #pragma unroll
         for (int c = 0; c < D; ++c) { dk[c] = 0.f; dvv[c] = 0.f; }
     }
-    for (int q0 = 0; q0 < L; q0 += KT) {
+    for (int q0 = 0; q0 < Lq; q0 += KT) {
         __syncthreads();
-        load_tile(Qs, qkn, 2 * E, head * D, q0, L);
-        load_tile(Os, don, E, head * D, q0, L);
+        load_tile(Qs, qn, ldq, head * D, q0, Lq);
+        load_tile(Os, don, E, head * D, q0, Lq);
         for (int r = threadIdx.x; r < KT; r += blockDim.x) {
-            const bool ok = q0 + r < L;
-            Ls[r] = ok ? lse[((long)n * nh + head) * L + q0 + r] : INFINITY;     // p = exp(s - inf) = 0 beyond L
-            Dsh[r] = ok ? Dbuf[((long)n * nh + head) * L + q0 + r] : 0.f;
+            const bool ok = q0 + r < Lq;
+            Ls[r] = ok ? lse[((long)n * nh + head) * Lq + q0 + r] : INFINITY;    // p = exp(s - inf) = 0 beyond Lq
+            Dsh[r] = ok ? Dbuf[((long)n * nh + head) * Lq + q0 + r] : 0.f;
         }
         __syncthreads();
-        const int nq = min(KT, L - q0);
+        const int nq = min(KT, Lq - q0);
         for (int r = g; r < nq; r += 4) {
             const float p = expf(dot32(kr, Qs + r * D) - Ls[r]);
             axpy32(dvv, p, Os + r * D);
@@ -256,8 +265,8 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
         dvv[c] = b;
     }
     if (jv) {
-        float* ok = dqk + ((long)n * L + j) * 2 * E + E + head * D + g * 8;
-        float* ov = dv + ((long)n * L + j) * E + head * D + g * 8;
+        float* ok = dk_out + ((long)n * Lk + j) * lddk + head * D + g * 8;
+        float* ov = dv + ((long)n * Lk + j) * lddv + head * D + g * 8;
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4) {
             *reinterpret_cast<float4*>(ok + c4 * 4) = make_float4(dk[g * 8 + c4 * 4 + 0], dk[g * 8 + c4 * 4 + 1],
@@ -358,26 +367,27 @@ __device__ __forceinline__ void store_own(float* __restrict__ row, int g, const 
 }
 __device__ __forceinline__ f32x16 zero16() { return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
 
-__global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qk, const float* __restrict__ v, float* __restrict__ o,
-                                                  float* __restrict__ lse, int N, int L, int nh, float scale) {
+__global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                  const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
+                                                  int Lq, int Lk, int nh, float scale) {
     __shared__ __attribute__((aligned(16))) __bf16 lds[2 * 2 * TILE];          // [buf][K | V^T]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* vn = v + (long)n * L * E;
+    const float* kn = kg + (long)n * Lk * ldk;
+    const float* vn = vg + (long)n * Lk * ldv;
     bf16x8 qh[2], ql[2];
-    own_frag(qkn + (long)min(q, L - 1) * 2 * E + head * D, g, scale, qh, ql);
+    own_frag(qg + ((long)n * Lq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
     float m = -INFINITY, l = 0.f;
     f32x16 OT = zero16();
     constexpr int PD = 3;                                                      // tiles in flight (register ring, statically indexed)
     struct Ring { NatRegs k; TrRegs v; } r0, r1, r2;          // separate variables, not an array: keeps them in registers
-    const int ntile = (L + 31) / 32;
+    const int ntile = (Lk + 31) / 32;
     auto fetch = [&](NatRegs& a, TrRegs& b, int t) __attribute__((always_inline)) {
         const int r0 = min(t, ntile - 1) * 32;                                 // surplus prefetches re-read the last tile
-        nat_fetch(a, qkn, 2 * E, E + head * D, r0, L, tid);
-        tr_fetch(b, vn, E, head * D, r0, L, lane);          // every wave loads (only wave 0 stages): keeps the ring in registers
+        nat_fetch(a, kn, ldk, head * D, r0, Lk, tid);
+        tr_fetch(b, vn, ldv, head * D, r0, Lk, lane);       // every wave loads (only wave 0 stages): keeps the ring in registers
     };
     auto stash = [&](const NatRegs& a, const TrRegs& b, int buf) __attribute__((always_inline)) {
         nat_stash(a, lds + buf * 2 * TILE, tid);
@@ -395,7 +405,7 @@ __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qk, 
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (t * 32 + reg_row(r, g) >= L) S[r] = -INFINITY;
+                if (t * 32 + reg_row(r, g) >= Lk) S[r] = -INFINITY;
                 mx = fmaxf(mx, S[r]);
             }
             mx = xhalf_max(mx);
@@ -421,9 +431,9 @@ __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qk, 
         step(r1, r2, t0 + 1);
         step(r2, r0, t0 + 2);
     }
-    if (q < L) {
-        store_own(o + ((long)n * L + q) * E + head * D, g, OT, 1.f / l);
-        if (g == 0) lse[((long)n * nh + head) * L + q] = m + logf(l);
+    if (q < Lq) {
+        store_own(o + ((long)n * Lq + q) * E + head * D, g, OT, 1.f / l);
+        if (g == 0) lse[((long)n * nh + head) * Lq + q] = m + logf(l);
     }
 }
 
@@ -431,8 +441,9 @@ __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qk, 
 // the second half, for the same 2 x 32 queries -- and merge their (running maximum, sum, O^T) through LDS at the end.  A wave's life is a chain of
 // [barrier, two dependent MFMA groups, a softmax update] per key tile with nobody to overlap with (160 waves on 1024 SIMDs at L = 300): half the steps per
 // wave.  Each half stages its own tiles (its two waves = the 128 staging threads of fwd_kernel), both halves share the barriers.
-__global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict__ qk, const float* __restrict__ v, float* __restrict__ o,
-                                                         float* __restrict__ lse, int N, int L, int nh, float scale) {
+__global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                         const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
+                                                         int Lq, int Lk, int nh, float scale) {
     __shared__ __attribute__((aligned(16))) __bf16 lds_all[2 * 2 * 2 * TILE];      // [key half][buf][K | V^T]
     const int E = nh * D;
     const int tid = threadIdx.x & (NTF - 1), lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
@@ -440,20 +451,20 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
     __bf16* lds = lds_all + kh * (2 * 2 * TILE);
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* vn = v + (long)n * L * E;
+    const float* kn = kg + (long)n * Lk * ldk;
+    const float* vn = vg + (long)n * Lk * ldv;
     bf16x8 qh[2], ql[2];
-    own_frag(qkn + (long)min(q, L - 1) * 2 * E + head * D, g, scale, qh, ql);
+    own_frag(qg + ((long)n * Lq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
     float m = -INFINITY, l = 0.f;
     f32x16 OT = zero16();
     constexpr int PD = 3;
     struct Ring { NatRegs k; TrRegs v; } r0, r1, r2;
-    const int ntile = (L + 31) / 32, nth = (ntile + 1) / 2;                     // tiles in all / per half (the second half may hold fewer)
+    const int ntile = (Lk + 31) / 32, nth = (ntile + 1) / 2;                     // tiles in all / per half (the second half may hold fewer)
     const int tbase = kh * nth, nmine = max(0, min(nth, ntile - tbase));
     auto fetch = [&](NatRegs& a, TrRegs& b, int t) __attribute__((always_inline)) {
         const int r0_ = min(tbase + min(t, max(nmine - 1, 0)), ntile - 1) * 32;   // surplus prefetches re-read this half's last tile
-        nat_fetch(a, qkn, 2 * E, E + head * D, r0_, L, tid);
-        tr_fetch(b, vn, E, head * D, r0_, L, lane);
+        nat_fetch(a, kn, ldk, head * D, r0_, Lk, tid);
+        tr_fetch(b, vn, ldv, head * D, r0_, Lk, lane);
     };
     auto stash = [&](const NatRegs& a, const TrRegs& b, int buf) __attribute__((always_inline)) {
         nat_stash(a, lds + buf * 2 * TILE, tid);
@@ -470,7 +481,7 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
             float mx = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if ((tbase + t) * 32 + reg_row(r, g) >= L) S[r] = -INFINITY;
+                if ((tbase + t) * 32 + reg_row(r, g) >= Lk) S[r] = -INFINITY;
                 mx = fmaxf(mx, S[r]);
             }
             mx = xhalf_max(mx);
@@ -504,7 +515,7 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
         for (int r = 0; r < 16; ++r) mrg[2 + r] = OT[r];
     }
     __syncthreads();
-    if (kh == 0 && q < L) {
+    if (kh == 0 && q < Lq) {
         const float m2 = mrg[0], l2 = mrg[1];
         const float mn = fmaxf(m, m2);
         const float c1 = (m == -INFINITY) ? 0.f : __expf(m - mn), c2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
@@ -512,8 +523,8 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
         f32x16 OM;
 #pragma unroll
         for (int r = 0; r < 16; ++r) OM[r] = OT[r] * c1 + mrg[2 + r] * c2;
-        store_own(o + ((long)n * L + q) * E + head * D, g, OM, 1.f / lt);
-        if (g == 0) lse[((long)n * nh + head) * L + q] = mn + logf(lt);
+        store_own(o + ((long)n * Lq + q) * E + head * D, g, OM, 1.f / lt);
+        if (g == 0) lse[((long)n * nh + head) * Lq + q] = mn + logf(lt);
     }
 }
 
@@ -526,40 +537,41 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
 // backward's default arithmetic, ops.PRECISION_BWD 3).  The recomputed scores S = Q K^T keep all three terms in both: p = exp(S - lse) against the
 // FORWARD's log-sum-exp turns an error of S into a relative error of every probability of the row.
 template <int TB>
-__device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict__ qk, const float* __restrict__ v, const float* __restrict__ o,
-                                           const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dqk,
-                                           int N, int L, int nh, float scale) {
+__device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                           const float* __restrict__ vg, long ldv, const float* __restrict__ o, const float* __restrict__ dO,
+                                           const float* __restrict__ lse, float* __restrict__ dq_out, long lddq, int Lq, int Lk, int nh,
+                                           float scale) {
     // lds: [buf][K | V | K^T]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const int qc = min(q, L - 1);
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* vn = v + (long)n * L * E;
+    const int qc = min(q, Lq - 1);
+    const float* kn = kg + (long)n * Lk * ldk;
+    const float* vn = vg + (long)n * Lk * ldv;
     bf16x8 qh[2], ql[2], dh[2], dl[2];
-    own_frag(qkn + (long)qc * 2 * E + head * D, g, scale, qh, ql);
-    const float* dop = dO + ((long)n * L + qc) * E + head * D;
+    own_frag(qg + ((long)n * Lq + qc) * ldq + head * D, g, scale, qh, ql);
+    const float* dop = dO + ((long)n * Lq + qc) * E + head * D;
     own_frag(dop, g, 1.f, dh, dl);
     float Di = 0.f;
     {
-        const float* op = o + ((long)n * L + qc) * E + head * D;
+        const float* op = o + ((long)n * Lq + qc) * E + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 8; ++c4) {
             const float4 u = ld4(dop + c4 * 4), w = ld4(op + c4 * 4);
             Di += (u.x * w.x + u.y * w.y) + (u.z * w.z + u.w * w.w);
         }
     }
-    const float li = lse[((long)n * nh + head) * L + qc];
+    const float li = lse[((long)n * nh + head) * Lq + qc];
     f32x16 dQT = zero16();
     constexpr int PD = 3;
     struct Ring { NatRegs k, v; TrRegs kt; } r0, r1, r2;
-    const int ntile = (L + 31) / 32;
+    const int ntile = (Lk + 31) / 32;
     auto fetch = [&](NatRegs& a, NatRegs& b, TrRegs& c, int t) __attribute__((always_inline)) {
         const int r0 = min(t, ntile - 1) * 32;
-        nat_fetch(a, qkn, 2 * E, E + head * D, r0, L, tid);
-        nat_fetch(b, vn, E, head * D, r0, L, tid);
-        tr_fetch(c, qkn, 2 * E, E + head * D, r0, L, lane);
+        nat_fetch(a, kn, ldk, head * D, r0, Lk, tid);
+        nat_fetch(b, vn, ldv, head * D, r0, Lk, tid);
+        tr_fetch(c, kn, ldk, head * D, r0, Lk, lane);
     };
     auto stash = [&](const NatRegs& a, const NatRegs& b, const TrRegs& c, int buf) __attribute__((always_inline)) {
         __bf16* nb = lds + buf * 3 * TILE;
@@ -579,7 +591,7 @@ __device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict_
             const f32x16 dP = mma_tile<TB>(zero16(), base + TILE, i32, g, dh, dl);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = (t * 32 + reg_row(r, g) < L) ? __expf(S[r] - li) : 0.f;
+                const float p = (t * 32 + reg_row(r, g) < Lk) ? __expf(S[r] - li) : 0.f;
                 S[r] = p * (dP[r] - Di);
             }
             bf16x8 sh[2], sl[2];
@@ -594,43 +606,45 @@ __device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict_
         step(r1, r2, t0 + 1);
         step(r2, r0, t0 + 2);
     }
-    if (q < L) {
-        store_own(dqk + ((long)n * L + q) * 2 * E + head * D, g, dQT, scale);
+    if (q < Lq) {
+        store_own(dq_out + ((long)n * Lq + q) * lddq + head * D, g, dQT, scale);
     }
 }
 
 template <int TB>
-__device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], const float* __restrict__ qk, const float* __restrict__ v,
+__device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], const float* __restrict__ qg, long ldq,
+                                            const float* __restrict__ kg, long ldk, const float* __restrict__ vg, long ldv,
                                             const float* __restrict__ o, const float* __restrict__ dO, const float* __restrict__ lse,
-                                            float* __restrict__ dqk, float* __restrict__ dv, int N, int L, int nh, float scale) {
+                                            float* __restrict__ dk_out, long lddk, float* __restrict__ dv, long lddv, int Lq, int Lk, int nh,
+                                            float scale) {
     // lds: [buf][Q | dO | Q^T | dO^T]; stat: [buf][lse | D][query of the tile]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int j = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const int jc = min(j, L - 1);
-    const float* qkn = qk + (long)n * L * 2 * E;
-    const float* don = dO + (long)n * L * E;
-    const float* on = o + (long)n * L * E;
-    const float* lsn = lse + ((long)n * nh + head) * L;
+    const int jc = min(j, Lk - 1);
+    const float* qn = qg + (long)n * Lq * ldq;
+    const float* don = dO + (long)n * Lq * E;
+    const float* on = o + (long)n * Lq * E;
+    const float* lsn = lse + ((long)n * nh + head) * Lq;
     bf16x8 kh[2], kl[2], vh[2], vl[2];
-    own_frag(qkn + (long)jc * 2 * E + E + head * D, g, scale, kh, kl);
-    own_frag(v + ((long)n * L + jc) * E + head * D, g, 1.f, vh, vl);
+    own_frag(kg + ((long)n * Lk + jc) * ldk + head * D, g, scale, kh, kl);
+    own_frag(vg + ((long)n * Lk + jc) * ldv + head * D, g, 1.f, vh, vl);
     f32x16 dKT = zero16(), dVT = zero16();
     constexpr int PD = 3;
-    const float* trsrc = (wid == 0) ? qkn : don;                               // wave 0 stages Q^T, wave 1 dO^T
-    const long trld = (wid == 0) ? 2 * E : E;
+    const float* trsrc = (wid == 0) ? qn : don;                                // wave 0 stages Q^T, wave 1 dO^T
+    const long trld = (wid == 0) ? ldq : E;
     struct Ring { NatRegs q, d, o; TrRegs t; float s; } r0, r1, r2;
-    const int ntile = (L + 31) / 32;
+    const int ntile = (Lq + 31) / 32;
     auto fetch = [&](Ring& r, int t) __attribute__((always_inline)) {
         const int r0 = min(t, ntile - 1) * 32;
-        nat_fetch(r.q, qkn, 2 * E, head * D, r0, L, tid);
-        nat_fetch(r.d, don, E, head * D, r0, L, tid);
-        nat_fetch(r.o, on, E, head * D, r0, L, tid);                        // the forward's output rows of the tile: D = rowsum(dO * O)
-        tr_fetch(r.t, trsrc, trld, head * D, r0, L, lane);
+        nat_fetch(r.q, qn, ldq, head * D, r0, Lq, tid);
+        nat_fetch(r.d, don, E, head * D, r0, Lq, tid);
+        nat_fetch(r.o, on, E, head * D, r0, Lq, tid);                      // the forward's output rows of the tile: D = rowsum(dO * O)
+        tr_fetch(r.t, trsrc, trld, head * D, r0, Lq, lane);
         const int qq = t * 32 + (tid & 31);                                // lse of the tile (lanes 0-31 of wave 0)
-        const float x = lsn[min(qq, L - 1)];                               // (true, unclamped index: surplus tiles must be inert)
-        r.s = (qq < L) ? x : INFINITY;                                     // p = exp(s - inf) = 0 beyond L
+        const float x = lsn[min(qq, Lq - 1)];                              // (true, unclamped index: surplus tiles must be inert)
+        r.s = (qq < Lq) ? x : INFINITY;                                    // p = exp(s - inf) = 0 beyond Lq
     };
     auto stash = [&](const Ring& r, int buf) __attribute__((always_inline)) {
         __bf16* nb = lds + buf * 4 * TILE;
@@ -639,7 +653,7 @@ __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], c
         tr_stash(r.t, nb + (wid == 0 ? 2 : 3) * TILE, lane);
         if (tid < 32) stat[buf][0][tid] = r.s;
         // D of the tile's 32 queries: thread (row = idx >> 3, 4 columns) holds a quarter-row product of dO and O; the 8 threads of a row
-        // are consecutive lanes (rows past L are clamped copies: their p is 0, any finite D will do)
+        // are consecutive lanes (rows past Lq are clamped copies: their p is 0, any finite D will do)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             float pd = (r.d.v[s2].x * r.o.v[s2].x + r.d.v[s2].y * r.o.v[s2].y) + (r.d.v[s2].z * r.o.v[s2].z + r.d.v[s2].w * r.o.v[s2].w);
@@ -686,53 +700,139 @@ __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], c
         step(r1, r2, t0 + 1);
         step(r2, r0, t0 + 2);
     }
-    if (j < L) {
-        store_own(dqk + ((long)n * L + j) * 2 * E + E + head * D, g, dKT, scale);
-        store_own(dv + ((long)n * L + j) * E + head * D, g, dVT, 1.f);
+    if (j < Lk) {
+        store_own(dk_out + ((long)n * Lk + j) * lddk + head * D, g, dKT, scale);
+        store_own(dv + ((long)n * Lk + j) * lddv + head * D, g, dVT, 1.f);
     }
 }
 
+// With Lq != Lk the grid is as wide as the longer side: the surplus workgroups of the shorter one exit at once (workgroup-uniform,
+// before any barrier).  Measured against two launches of exactly sized grids: see cdetr_attn_bwd.
 template <int TB>
-__global__ __launch_bounds__(NTF) void bwd_kernel(const float* __restrict__ qk, const float* __restrict__ v, const float* __restrict__ o,
-                                                  const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dqk,
-                                                  float* __restrict__ dv, int N, int L, int nh, float scale) {
+__global__ __launch_bounds__(NTF) void bwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
+                                                  const float* __restrict__ vg, long ldv, const float* __restrict__ o,
+                                                  const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dq,
+                                                  long lddq, float* __restrict__ dk, long lddk, float* __restrict__ dv, long lddv, int Lq,
+                                                  int Lk, int nh, float scale, int zbase) {
     __shared__ __attribute__((aligned(16))) __bf16 lds[2 * 4 * TILE];
     __shared__ __attribute__((aligned(16))) float stat[2][2][32];
-    if (blockIdx.z == 0) bwd_q_body<TB>(lds, qk, v, o, dO, lse, dqk, N, L, nh, scale);
-    else bwd_kv_body<TB>(lds, stat, qk, v, o, dO, lse, dqk, dv, N, L, nh, scale);
+    const int z = blockIdx.z + zbase;
+    if ((int)blockIdx.x * 32 * NWF >= (z == 0 ? Lq : Lk)) return;
+    if (z == 0) bwd_q_body<TB>(lds, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dq, lddq, Lq, Lk, nh, scale);
+    else bwd_kv_body<TB>(lds, stat, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dk, lddk, dv, lddv, Lq, Lk, nh, scale);
 }
 }  // namespace flash
+
+
+// ------------------------------------------------------------------------------------------------------------ launches
+struct Operands {
+    const float *q, *k, *v;
+    long ldq, ldk, ldv;
+    int N, Lq, Lk, nh;
+    float scale;
+};
+
+void launch_fwd(const Operands& a, float* o, float* lse, bool mfma, bool key_split, hipStream_t st) {
+    const dim3 grid((a.Lq + 63) / 64, a.N * a.nh);
+    if (mfma && key_split)
+        hipLaunchKernelGGL(flash::fwd_ks_kernel, grid, dim3(2 * flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+    else if (mfma)
+        hipLaunchKernelGGL(flash::fwd_kernel, grid, dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+    else
+        hipLaunchKernelGGL(mha_fwd_kernel, grid, dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+}
+
+// tb: 0 = the two fp32 VALU launches (D through `work`), 3 / 1 = one flash::bwd_kernel launch with split-bf16 / plain-bf16 gradient contractions
+void launch_bwd(const Operands& a, const float* o, const float* d_o, const float* lse, float* dq, long lddq, float* dk, long lddk, float* dv,
+                long lddv, float* work, int tb, bool two_launches, hipStream_t st) {
+    const int gq = (a.Lq + 63) / 64, gk = (a.Lk + 63) / 64, nb = a.N * a.nh;
+    if (tb == 0) {
+        hipLaunchKernelGGL(mha_bwd_q_kernel, dim3(gq, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, work,
+                           a.Lq, a.Lk, a.nh, a.scale);
+        hipLaunchKernelGGL(mha_bwd_kv_kernel, dim3(gk, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, d_o, lse, work, dk, lddk,
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale);
+        return;
+    }
+    auto kern = (tb == 1) ? flash::bwd_kernel<1> : flash::bwd_kernel<3>;
+    if (two_launches) {
+        hipLaunchKernelGGL(kern, dim3(gq, nb, 1), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, dk, lddk,
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0);
+        hipLaunchKernelGGL(kern, dim3(gk, nb, 1), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, dk, lddk,
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 1);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(max(gq, gk), nb, 2), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq,
+                           dk, lddk, dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0);
+    }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
 extern "C" int cdetr_mha_fwd(const float* qk, const float* v, float* o, float* lse, int32_t N, int32_t L, int32_t nh, float scale,
                              int32_t precision, void* stream) {
     CDETR_CHECK_ARG(qk && v && o && lse && N > 0 && L > 0 && nh > 0, "cdetr_mha_fwd: bad args");
-    dim3 grid((L + 63) / 64, N * nh);
     static const int use_mfma = getenv("CDETR_MHA_MFMA") ? atoi(getenv("CDETR_MHA_MFMA")) : 1;
     static const int key_split = getenv("CDETR_MHA_KEY_SPLIT") ? atoi(getenv("CDETR_MHA_KEY_SPLIT")) : 1;      // A/B: 0 = two waves walk all key tiles
-    if (use_mfma && precision == 1 && key_split && L >= 128)
-        hipLaunchKernelGGL(flash::fwd_ks_kernel, grid, dim3(2 * flash::NTF), 0, reinterpret_cast<hipStream_t>(stream), qk, v, o, lse, N, L, nh, scale);
-    else if (use_mfma && precision == 1) hipLaunchKernelGGL(flash::fwd_kernel, grid, dim3(flash::NTF), 0, reinterpret_cast<hipStream_t>(stream), qk, v, o, lse, N, L, nh, scale);
-    else hipLaunchKernelGGL(mha_fwd_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), qk, v, o, lse, N, L, nh, scale);
+    const long E = (long)nh * D;
+    const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
+    const bool mfma = use_mfma && precision == 1;
+    launch_fwd(a, o, lse, mfma, mfma && key_split && L >= 128, reinterpret_cast<hipStream_t>(stream));
     return cdetr_launch_status("cdetr_mha_fwd");
 }
 
 extern "C" int cdetr_mha_bwd(const float* qk, const float* v, const float* o, const float* d_o, const float* lse, float* d_qk,
                              float* d_v, float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision, void* stream) {
     CDETR_CHECK_ARG(qk && v && o && d_o && lse && d_qk && d_v && work && N > 0 && L > 0 && nh > 0, "cdetr_mha_bwd: bad args");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((L + 63) / 64, N * nh);
     static const int use_mfma = getenv("CDETR_MHA_MFMA") ? atoi(getenv("CDETR_MHA_MFMA")) : 1;
-    if (use_mfma && precision == 3) {      // split-bf16 scores, plain-bf16 gradient contractions (flash::bwd_q_body)
-        hipLaunchKernelGGL(flash::bwd_kernel<1>, dim3(grid.x, grid.y, 2), dim3(flash::NTF), 0, st, qk, v, o, d_o, lse, d_qk, d_v, N, L, nh, scale);
-        return cdetr_launch_status("cdetr_mha_bwd");
-    }
-    if (use_mfma && precision == 1) {
-        hipLaunchKernelGGL(flash::bwd_kernel<3>, dim3(grid.x, grid.y, 2), dim3(flash::NTF), 0, st, qk, v, o, d_o, lse, d_qk, d_v, N, L, nh, scale);
-        return cdetr_launch_status("cdetr_mha_bwd");
-    }
-    hipLaunchKernelGGL(mha_bwd_q_kernel, grid, dim3(256), 0, st, qk, v, o, d_o, lse, d_qk, work, N, L, nh, scale);
-    hipLaunchKernelGGL(mha_bwd_kv_kernel, grid, dim3(256), 0, st, qk, v, d_o, lse, work, d_qk, d_v, N, L, nh, scale);
+    const long E = (long)nh * D;
+    const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
+    // precision 3: split-bf16 scores, plain-bf16 gradient contractions (flash::bwd_q_body); 1: split-bf16 throughout; else fp32
+    const int tb = (use_mfma && precision == 3) ? 1 : (use_mfma && precision == 1) ? 3 : 0;
+    launch_bwd(a, o, d_o, lse, d_qk, 2 * E, d_qk + E, 2 * E, d_v, E, work, tb, false, reinterpret_cast<hipStream_t>(stream));
     return cdetr_launch_status("cdetr_mha_bwd");
+}
+
+// Forward kernel choice for the general problem: the key split (fwd_ks_kernel) from 128 keys on, as for cdetr_mha_fwd.  Measured at N = 2,
+// nh = 8 (tools/attn_ab.py, median of 50 launches, fwd_kernel -> fwd_ks_kernel): 300 x 864 keys 43 -> 31 us, 300 x 2500 99 -> 61, 900 x 2500
+// 102 -> 65, 2500 x 2500 153 -> 133: with up to 40 query tiles per (image, head) the grid still leaves the chip half empty or runs one round
+// of waves, and halving each wave's chain of key tiles wins at every size the variant meets.  The backward's one launch (bwd_kernel, grid
+// as wide as the longer side) against two exactly sized launches: 300 x 864 81 vs 98 us, 900 x 2500 190 vs 234, 2500 x 2500 385 vs 478 --
+// one launch lets the query and key halves share the chip.
+static bool attn_key_split(int Lk) {
+    static const int force = getenv("CDETR_ATTN_KEY_SPLIT") ? atoi(getenv("CDETR_ATTN_KEY_SPLIT")) : -1;     // A/B: 0 / 1 forces the choice
+    if (force >= 0) return force != 0;
+    return Lk >= 128;
+}
+
+static int attn_check(const cdetr_attn_desc* d, const char* what) {
+    CDETR_CHECK_ARG(d && d->q && d->k && d->v && d->o && d->lse && d->N > 0 && d->Lq > 0 && d->Lk > 0 && d->nh > 0, "%s: bad args", what);
+    const long E = (long)d->nh * D;
+    CDETR_CHECK_ARG(d->ldq >= E && d->ldk >= E && d->ldv >= E && d->ldq % 4 == 0 && d->ldk % 4 == 0 && d->ldv % 4 == 0,
+                    "%s: row strides must be multiples of 4 floats and at least nh * 32", what);
+    CDETR_CHECK_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->o), "%s: operands must be 16-byte aligned", what);
+    CDETR_CHECK_ARG(d->precision == 0 || d->precision == 1 || d->precision == 3, "%s: precision must be 0, 1 or 3", what);
+    return 0;
+}
+
+extern "C" int cdetr_attn_fwd(const cdetr_attn_desc* d, void* stream) {
+    if (int rc = attn_check(d, "cdetr_attn_fwd")) return rc;
+    const Operands a{d->q, d->k, d->v, d->ldq, d->ldk, d->ldv, d->N, d->Lq, d->Lk, d->nh, d->scale};
+    const bool mfma = d->precision != 0;
+    launch_fwd(a, d->o, d->lse, mfma, mfma && attn_key_split(d->Lk), reinterpret_cast<hipStream_t>(stream));
+    return cdetr_launch_status("cdetr_attn_fwd");
+}
+
+extern "C" int cdetr_attn_bwd(const cdetr_attn_desc* d, void* stream) {
+    if (int rc = attn_check(d, "cdetr_attn_bwd")) return rc;
+    const long E = (long)d->nh * D;
+    CDETR_CHECK_ARG(d->d_o && d->d_q && d->d_k && d->d_v && (d->precision != 0 || d->work), "cdetr_attn_bwd: bad args");
+    CDETR_CHECK_ARG(d->ld_dq >= E && d->ld_dk >= E && d->ld_dv >= E && d->ld_dq % 4 == 0 && d->ld_dk % 4 == 0 && d->ld_dv % 4 == 0 &&
+                    aligned16(d->d_o) && aligned16(d->d_q) && aligned16(d->d_k) && aligned16(d->d_v),
+                    "cdetr_attn_bwd: gradient row strides must be multiples of 4 floats and at least nh * 32, gradients 16-byte aligned");
+    static const int two = getenv("CDETR_ATTN_BWD_TWO_LAUNCHES") ? atoi(getenv("CDETR_ATTN_BWD_TWO_LAUNCHES")) : 0;   // A/B
+    const Operands a{d->q, d->k, d->v, d->ldq, d->ldk, d->ldv, d->N, d->Lq, d->Lk, d->nh, d->scale};
+    const int tb = d->precision == 3 ? 1 : d->precision == 1 ? 3 : 0;
+    launch_bwd(a, d->o, d->d_o, d->lse, d->d_q, d->ld_dq, d->d_k, d->ld_dk, d->d_v, d->ld_dv, d->work, tb, two != 0, reinterpret_cast<hipStream_t>(stream));
+    return cdetr_launch_status("cdetr_attn_bwd");
 }

@@ -304,6 +304,12 @@ def _scoped(fn):
     return wrapper
 
 
+def model_unused_prefixes(model):
+    """Parameter-name prefixes the model's configuration leaves out of the loss (the transformer's `unused_prefixes`, e.g. adapt_pos1d for
+    attention_type "nn.MultiheadAttention"), as full names."""
+    return tuple(f"{n}.{p}" for n, m in model.named_modules() if n for p in getattr(m, "unused_prefixes", ()))
+
+
 class Trainer:
     # parameters the model builds but the loss never reaches: their gradient stays None in the reference, so the optimizer leaves them alone
     # (torch's AdamW skips a parameter without a gradient, weight decay included) -- they are kept out of the flat arena
@@ -318,6 +324,7 @@ class Trainer:
         self.device = torch.device(device or args.device)
         self.max_norm = args.clip_max_norm
         self.betas, self.eps, self.wd = (0.9, 0.999), 1e-8, args.weight_decay
+        self.unused_prefixes = tuple(self.unused_prefixes) + model_unused_prefixes(model)
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and not n.startswith(self.unused_prefixes)]
         for n, p in model.named_parameters():
             if n.startswith(self.unused_prefixes):

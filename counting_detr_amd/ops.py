@@ -1293,6 +1293,89 @@ def mha_core(qk, v, nh):
     return MhaCoreFn.apply(qk, v, nh)
 
 
+# ----------------------------------------------------------------------------------------------------- general attention core
+def _attn_rows(t):
+    """(t', row stride) for an [N, L, E] operand read in place by cdetr_attn_*: unit column stride, 16-byte aligned rows, image n at row n*L."""
+    N, L, E = t.shape
+    ld = t.stride(1) if L > 1 else (t.stride(0) if N > 1 else E)
+    if t.stride(2) != 1 or ld < E or ld % 4 or (N > 1 and t.stride(0) != L * ld) or t.data_ptr() & 15:
+        t = t.contiguous()
+        ld = E
+    return t, ld
+
+
+def _attn_desc(q, ldq, k, ldk, v, ldv, N, Lq, Lk, nh, precision):
+    d = _ffi.AttnDesc()
+    d.q, d.k, d.v = q, k, v
+    d.ldq, d.ldk, d.ldv = ldq, ldk, ldv
+    d.N, d.Lq, d.Lk, d.nh = N, Lq, Lk, nh
+    d.scale = 32 ** -0.5
+    d.precision = precision
+    return d
+
+
+class AttnCoreFn(torch.autograd.Function):
+    """softmax(q k^T / sqrt(32)) v per head without masks (cdetr_attn_fwd / _bwd), Lq queries against Lk keys.  `k is None`: q is the
+    packed [N,L,2E] projection q | k (the encoder's self-attention) and its gradient is ONE [N,L,2E] tensor; else q [N,Lq,E], k [N,Lk,E]
+    (any row stride).  v [N,Lk,E].  Capture-safe: allocations and launches only, no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nh):
+        E = v.shape[-1]
+        assert E == nh * 32, "the attention kernels are specialised for head_dim 32"
+        packed = k is None
+        if packed:
+            assert q.shape[-1] == 2 * E
+            q = q.contiguous()
+            N, Lq, _ = q.shape
+            Lk, ldq, ldk = Lq, 2 * E, 2 * E
+            qp, kp = q.data_ptr(), q.data_ptr() + 4 * E
+        else:
+            q, ldq = _attn_rows(q)
+            k, ldk = _attn_rows(k)
+            N, Lq, _ = q.shape
+            Lk = k.shape[1]
+            qp, kp = ptr(q), ptr(k)
+        assert v.shape[:2] == (N, Lk)
+        v, ldv = _attn_rows(v)
+        o = torch.empty((N, Lq, E), device=v.device, dtype=torch.float32)
+        lse = torch.empty((N, nh, Lq), device=v.device, dtype=torch.float32)
+        d = _attn_desc(qp, ldq, kp, ldk, ptr(v), ldv, N, Lq, Lk, nh, PRECISION)
+        d.o, d.lse = ptr(o), ptr(lse)
+        check(lib().cdetr_attn_fwd(C.byref(d), stream_ptr()), "cdetr_attn_fwd")
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.cfg = (packed, nh, N, Lq, Lk, ldq, ldk, ldv)
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        q, k, v, o, lse = ctx.saved_tensors
+        packed, nh, N, Lq, Lk, ldq, ldk, ldv = ctx.cfg
+        E = v.shape[-1]
+        d_o = d_o.contiguous()
+        prec = bwd_precision() if MHA_BWD_BF16 else PRECISION      # the decoder self-attention's rule (see MHA_BWD_BF16)
+        if packed:
+            d_q = torch.empty_like(q)
+            d_k = None
+            qp, kp, dqp, dkp, lddq, lddk = q.data_ptr(), q.data_ptr() + 4 * E, d_q.data_ptr(), d_q.data_ptr() + 4 * E, 2 * E, 2 * E
+        else:
+            d_q = torch.empty((N, Lq, E), device=v.device, dtype=torch.float32)
+            d_k = torch.empty((N, Lk, E), device=v.device, dtype=torch.float32)
+            qp, kp, dqp, dkp, lddq, lddk = ptr(q), ptr(k), ptr(d_q), ptr(d_k), E, E
+        d_v = torch.empty((N, Lk, E), device=v.device, dtype=torch.float32)
+        work = torch.empty((N, nh, Lq), device=v.device, dtype=torch.float32) if prec == 0 else None
+        d = _attn_desc(qp, ldq, kp, ldk, ptr(v), ldv, N, Lq, Lk, nh, prec)
+        d.o, d.lse, d.d_o, d.d_q, d.d_k, d.d_v, d.work = ptr(o), ptr(lse), ptr(d_o), dqp, dkp, ptr(d_v), ptr(work)
+        d.ld_dq, d.ld_dk, d.ld_dv = lddq, lddk, E
+        check(lib().cdetr_attn_bwd(C.byref(d), stream_ptr()), "cdetr_attn_bwd")
+        return d_q, d_k, d_v, None
+
+
+def attn_core(q, k, v, nh):
+    """AttnCoreFn: k None = q is the packed [N,L,2E] q | k projection."""
+    return AttnCoreFn.apply(q, k, v, nh)
+
+
 # ----------------------------------------------------------------------------------------------------- layer norm & glue
 GN_SPLIT = os.environ.get("CDETR_GN_SPLIT", "1") != "0"      # A/B: 0 = one workgroup per (image, group)
 

@@ -80,6 +80,8 @@ def build(args):
     """A1/models/anchor_detr.py:375-409."""
     from . import _ffi
     _ffi.lib()
+    if args.attention_type != "RCDA":
+        raise NotImplementedError(f"stage 1 is implemented for attention_type 'RCDA' only, not {args.attention_type!r}")
     backbone = BackboneAgg(args.lr_backbone > 0, args.dilation)
     transformer = Transformer(d_model=args.hidden_dim, nhead=args.nheads, num_encoder_layers=args.enc_layers,
                               num_decoder_layers=args.dec_layers, dim_feedforward=args.dim_feedforward, dropout=args.dropout,

@@ -183,6 +183,33 @@ class MultiheadSelfAttention(nn.Module):
         return self.out_proj(o, resid=resid)
 
 
+class MultiheadAttention(nn.Module):
+    """nn.MultiheadAttention(E, nh) without masks, as attention_type "nn.MultiheadAttention" uses it for the encoder self-attention and the
+    decoder cross-attention (A2/models/transformer.py:223-228,262-272,324-330,393-398; same parameter names and shapes).  Projections run on
+    the MFMA GEMM kernel, the softmax(QK^T)V core on the flash kernels (ops.attn_core) for any query / key lengths."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        assert embed_dim == num_heads * 32, "the attention kernels are specialised for head_dim 32"
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, query, key, value, resid=None):
+        """Batch-first: query [N,Lq,E], key / value [N,Lk,E]; `key is None`: the keys are projected from `query` too (self-attention: q and
+        k in one GEMM).  Returns out_proj(attn) (+ resid) [N,Lq,E]."""
+        E, W, b = self.embed_dim, self.in_proj_weight, self.in_proj_bias
+        if key is None:
+            q, k = ops.linear(query, W, b, rows=(0, 2 * E)), None
+        else:
+            q, k = ops.linear(query, W, b, rows=(0, E)), ops.linear(key, W, b, rows=(E, 2 * E))
+        v = ops.linear(value, W, b, rows=(2 * E, 3 * E))
+        return self.out_proj(ops.attn_core(q, k, v, self.num_heads), resid=resid)
+
+
 class TransformerEncoderLayerSpatial(nn.Module):
     """A2/models/transformer.py:218-279, NHWC in / NHWC out."""
 
@@ -211,6 +238,23 @@ class TransformerEncoderLayerSpatial(nn.Module):
         return self.ffn(src)
 
 
+class TransformerEncoderLayerMHA(nn.Module):
+    """A2/models/transformer.py:218-279 with attention_type "nn.MultiheadAttention": self-attention over all h*w tokens (padded ones
+    included, no key mask), q = k = src + posemb_2d, v = src.  NHWC in / NHWC out."""
+
+    def __init__(self, d_model=256, d_ffn=1024, n_heads=8):
+        super().__init__()
+        self.self_attn = MultiheadAttention(d_model, n_heads)
+        self.norm1 = LayerNorm(d_model)
+        self.ffn = FFN(d_model, d_ffn)
+
+    def forward(self, src, posemb_2d):
+        N, H, W, Cc = src.shape
+        x = src.reshape(N, H * W, Cc)
+        a = self.self_attn((src + posemb_2d).reshape(N, H * W, Cc), None, x, resid=x)
+        return self.ffn(self.norm1(a).reshape(N, H, W, Cc))
+
+
 class TransformerDecoderLayer(nn.Module):
     """A2/models/transformer.py:316-409 (single feature level)."""
 
@@ -230,23 +274,51 @@ class TransformerDecoderLayer(nn.Module):
         return self.ffn(tgt)
 
 
+class TransformerDecoderLayerMHA(nn.Module):
+    """A2/models/transformer.py:316-409 with attention_type "nn.MultiheadAttention" (single feature level): the cross-attention takes
+    q = tgt + query_pos, k = memory + posemb_2d, v = memory over all h*w positions, without a key mask."""
+
+    def __init__(self, d_model=256, d_ffn=1024, n_heads=8):
+        super().__init__()
+        self.cross_attn = MultiheadAttention(d_model, n_heads)
+        self.norm1 = LayerNorm(d_model)
+        self.self_attn = MultiheadSelfAttention(d_model, n_heads)
+        self.norm2 = LayerNorm(d_model)
+        self.ffn = FFN(d_model, d_ffn)
+
+    def forward(self, tgt, query_pos, memory_pos, memory):
+        """tgt, query_pos [B,Q,C]; memory_pos = memory + posemb_2d and memory [B,h*w,C]."""
+        tgt = self.norm2(self.self_attn(tgt + query_pos, tgt, resid=tgt))                        # :369-372
+        tgt = self.norm1(self.cross_attn(tgt + query_pos, memory_pos, memory, resid=tgt))        # :393-407
+        return self.ffn(tgt)
+
+
+ATTENTION_TYPES = ("RCDA", "nn.MultiheadAttention")
+
+
 class Transformer(nn.Module):
-    """A2/models/transformer.py:21-215 for num_feature_levels == 1, attention_type == 'RCDA'."""
+    """A2/models/transformer.py:21-215 for num_feature_levels == 1, attention_type 'RCDA' (the fused stacks) or 'nn.MultiheadAttention'
+    (op-by-op autograd over the general attention kernels; stage 2 only)."""
 
     def __init__(self, d_model=256, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=1024,
                  dropout=0.0, activation="relu", num_feature_levels=1, num_query_position=300, num_query_pattern=3,
                  spatial_prior="learned", attention_type="RCDA", stage=2):
         super().__init__()
-        assert num_feature_levels == 1 and attention_type == "RCDA" and dropout == 0.0 and activation == "relu"
+        assert num_feature_levels == 1 and dropout == 0.0 and activation == "relu"
+        if attention_type not in ATTENTION_TYPES:
+            raise ValueError(f"unknown {attention_type} attention_type")
+        if attention_type != "RCDA" and stage != 2:
+            raise NotImplementedError(f"attention_type {attention_type!r} is implemented for stage 2 only")
         self.d_model, self.nhead, self.stage = d_model, nhead, stage
+        self.attention_type = attention_type
         self.all_layer_heads = True     # AnchorDETR sets this to its aux_loss flag
         self.taps = None                # see AnchorDETR.taps
         import os
         self.fused_decoder = os.environ.get("CDETR_FUSED_DECODER", "1") != "0"   # all decoder layers as one autograd node (ops.DecoderStackFn); False = op-by-op autograd
-        self.encoder_layers = nn.ModuleList(
-            TransformerEncoderLayerSpatial(d_model, dim_feedforward, nhead) for _ in range(num_encoder_layers))
-        self.decoder_layers = nn.ModuleList(
-            TransformerDecoderLayer(d_model, dim_feedforward, nhead) for _ in range(num_decoder_layers))
+        enc_cls, dec_cls = ((TransformerEncoderLayerSpatial, TransformerDecoderLayer) if attention_type == "RCDA" else
+                            (TransformerEncoderLayerMHA, TransformerDecoderLayerMHA))
+        self.encoder_layers = nn.ModuleList(enc_cls(d_model, dim_feedforward, nhead) for _ in range(num_encoder_layers))
+        self.decoder_layers = nn.ModuleList(dec_cls(d_model, dim_feedforward, nhead) for _ in range(num_decoder_layers))
         self.spatial_prior = spatial_prior
         self.num_pattern = num_query_pattern
         if stage == 2:
@@ -277,6 +349,12 @@ class Transformer(nn.Module):
             nn.init.constant_(bbox_variance.layers[-1].weight.data, 0.01)                             # :97-98
             nn.init.constant_(bbox_variance.layers[-1].bias.data, 0.01)
             self.bbox_variance = nn.ModuleList([bbox_variance for _ in range(num_decoder_layers)])
+
+    @property
+    def unused_prefixes(self):
+        """Parameters (names relative to this module) the loss never reaches in this configuration: the reference leaves their gradient
+        None, so AdamW neither updates nor decays them.  nn.MultiheadAttention builds adapt_pos1d and never calls it (:149-157)."""
+        return ("adapt_pos1d.",) if self.attention_type != "RCDA" else ()
 
     def reference_points(self, bs, device, points=None):
         """:114-135."""
@@ -317,6 +395,8 @@ class Transformer(nn.Module):
         else:
             tgt = (pattern.weight.reshape(1, self.num_pattern, 1, c).repeat(bs, 1, self.num_position, 1)
                    .reshape(bs, self.num_pattern * self.num_position, c))
+        if self.attention_type != "RCDA":
+            return self._heads(self._layers_mha(src, mi, reference_points, tgt), reference_points)
         # the four 1-d positional MLP applications (key rows / columns, query x / y) run level by level, grouped
         emb_x, emb_y = ops.sine_embed_xy(reference_points, c)
         posemb_row, posemb_col, query_pos_x, query_pos_y = pos_mlp_many(
@@ -361,6 +441,29 @@ class Transformer(nn.Module):
             for layer in self.decoder_layers:
                 output = layer(output, query_pos, query_pos_x, query_pos_y, memory, k_row_mean, k_col_mean, mask_row, mask_col)
                 layer_outs.append(output)
+        return self._heads(layer_outs, reference_points)
+
+    def _layers_mha(self, src, mi, reference_points, tgt):
+        """Encoder and decoder of attention_type "nn.MultiheadAttention" (:149-157, 262-272, 393-398); returns every decoder layer's output."""
+        bs, h, w, c = src.shape
+        # pos_2d [B,h,w,2] = (x, y) of every position, from mask2pos's column (x) and row (y) coordinates
+        pos_2d = torch.stack([mi.pos_row[:, None, :].expand(bs, h, w), mi.pos_col[:, :, None].expand(bs, h, w)], dim=-1)
+        posemb_2d, query_pos = pos_mlp_many(self.adapt_pos2d, [pos2posemb2d(pos_2d), pos2posemb2d(reference_points)])
+        memory = src
+        for li, layer in enumerate(self.encoder_layers):
+            memory = layer(memory, posemb_2d)
+            if self.taps is not None:
+                self.taps[f"enc{li}"] = memory.detach()
+        memory = memory.reshape(bs, h * w, c)
+        memory_pos = memory + posemb_2d.reshape(bs, h * w, c)        # the decoder's keys: shared by its layers
+        layer_outs, output = [], tgt
+        for layer in self.decoder_layers:
+            output = layer(output, query_pos, memory_pos, memory)
+            layer_outs.append(output)
+        return layer_outs
+
+    def _heads(self, layer_outs, reference_points):
+        last = len(self.decoder_layers) - 1
         if self.taps is not None:
             for lid, o in enumerate(layer_outs):
                 self.taps[f"hs{lid}"] = o.detach()

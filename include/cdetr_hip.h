@@ -360,6 +360,34 @@ int cdetr_mha_fwd(const float* qk, const float* v, float* o, float* lse, int32_t
 int cdetr_mha_bwd(const float* qk, const float* v, const float* o, const float* d_o, const float* lse, float* d_qk, float* d_v,
                   float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision, void* stream);
 
+/* ---- general attention core (nn.MultiheadAttention(256, 8) without masks: the encoder self-attention over all h*w tokens and the
+ * decoder cross-attention from Q queries to h*w keys of attention_type "nn.MultiheadAttention", A2/models/transformer.py:262-272,393-398)
+ * o = softmax(scale * q k^T) v per head, head dim 32, E = nh*32.  q: N images of Lq rows, row stride ldq (image n starts at row n*Lq);
+ * k, v: N images of Lk rows, row strides ldk, ldv; head h reads columns 32h .. 32h+31 of a row.  The strides let q and k be the two halves of
+ * one packed [N][L][2E] projection (k = q + E, ldq = ldk = 2E; cdetr_mha_* is exactly that instance) or separate tensors.  Strides are
+ * multiples of 4 floats, pointers 16-byte aligned.  o [N][Lq][E] and lse [N][nh][Lq] (the row log-sum-exp, saved for the backward) are
+ * dense.  Any Lq, Lk >= 1: rows past either length are masked arithmetically.
+ * cdetr_attn_fwd: reads q, k, v; writes o, lse.  precision 0 = fp32 (VALU), 1 or 3 = split-bf16 x3 MFMA.
+ * cdetr_attn_bwd: reads q, k, v, o, lse and d_o [N][Lq][E]; writes d_q, d_k, d_v (rows like q, k, v, with their own strides ld_dq,
+ * ld_dk, ld_dv: d_q and d_k may be the halves of one packed [N][L][2E] buffer).  precision 0 = fp32 in two launches (work: N*nh*Lq
+ * floats of scratch), 1 = split-bf16 x3 throughout, 3 = scores recomputed in split-bf16 x3 and the four gradient contractions in
+ * plain bf16 (as cdetr_mha_bwd); 1 and 3 are ONE launch whose query-side workgroups write d_q and whose key-side workgroups write
+ * d_k, d_v, and leave `work` untouched.                                                                                                 */
+typedef struct {
+    const float* q; const float* k; const float* v;
+    int64_t ldq, ldk, ldv;
+    float* o; float* lse;
+    const float* d_o;                   /* backward only */
+    float* d_q; float* d_k; float* d_v;
+    int64_t ld_dq, ld_dk, ld_dv;
+    float* work;                        /* backward, precision 0 only */
+    int32_t N, Lq, Lk, nh;
+    float scale;
+    int32_t precision;
+} cdetr_attn_desc;
+int cdetr_attn_fwd(const cdetr_attn_desc* d, void* stream);
+int cdetr_attn_bwd(const cdetr_attn_desc* d, void* stream);
+
 /* ---- Hungarian matcher (A2/models/matcher.py:197-247 + scipy.optimize.linear_sum_assignment) -------------
  * cdetr_match_cost: per image b, cost[b] = 5*L1 + 2*focal-class + 2*(-GIoU) in fp32 with the reference's expression
  * order, written in SOLVER layout: [nr][nc] with nr = min(Q,T_b), nc = max(Q,T_b) (transposed when T_b < Q,
