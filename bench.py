@@ -8,10 +8,14 @@ batch of 2 images 800x800 per GPU (Q=300 learned anchors, T=(37,120) targets -- 
 inputs resident in HBM, random-init (name-seeded) weights.  Weak scaling: per-GPU batch fixed, gradients averaged over
 ranks by RCCL in four buckets that leave while the backbone's backward is still running (stream-ordered step: from hooks in
 the backward; graph replay: between the five captured sub-graphs).
-Prints ONE JSON line on rank 0 with the extra objects `roofline` (implicit-GEMM family timed with HIP events on the launch
-stream in an instrumented eager pass of the same step), `step_ms` (median / p10 / p90 of the timed steps, HIP events),
-`extra_shapes` (the shipped script's grid-576 shape and a 384x576 image), at N>1 `allreduce_exposed_ms`, and at N=1
-`cpu_baseline` (the oracle's CPU restatement of the same step on the host's physical cores, bounded sample).
+A plain run sets up (model, launch-mode probe; at N>1 the exchange-form A/B), warms up, times --steps steps, writes --dump-outputs
+and prints ONE JSON line on rank 0: `value` / `ms_per_step`, `step_ms` (median / p10 / p90 of the timed steps, HIP events),
+`config`, `streams`, and at N>1 `exchange_variants` and `allreduce_exposed_ms`.
+--full then measures, in the same process, what takes runs of its own: `roofline` (implicit-GEMM family timed with HIP events on the
+launch stream in an instrumented eager pass of the same step), `frozen_stage_prefetch` (the same step with its frozen stage in line),
+and at N=1 `alt_precision`, `extra_shapes` (the shipped script's grid-576 shape, 384x576 images, crowded images, 800x1333),
+`inference`, `stage1_pseudo_labels`, `real_data_loop` and `cpu_baseline` (the oracle's CPU restatement of the same step on the
+host's physical cores, bounded sample); each of those at N=1 can be skipped with its --no-* option.
 --steps is the number of timed steps; --dump-outputs DIR then runs the timed path's step once more from the seeded starting state,
 untimed, and writes what it computed as .npy files (dump_step, dump_outputs).
 """
@@ -446,6 +450,122 @@ def real_data_leg(dev, precision, batch=2, reps=4):
             "device_memory_reserved_GB": torch.cuda.memory_reserved() / 2 ** 30}
 
 
+def roofline_leg(trainer, images, rects, targets, a, Q, ms_per_step, rank):
+    """--full: the `roofline` object -- same fwd+bwd, eager, every matrix-core launch bracketed by HIP events on its own stream."""
+    from counting_detr_amd import ops
+    H, W = a.size
+    import counting_detr_amd.backbone as bb
+    hook = bb._BACKWARD_HOOK
+    bb.set_backward_hook(None)
+    nb = float(sum(len(t_["boxes"]) for t_ in targets))
+    from counting_detr_amd.misc import nested_tensor_from_tensor_list
+    im, mk = nested_tensor_from_tensor_list(images).decompose()
+    reps = 2
+    prof = []
+    with ops.arithmetic(*trainer.arith), ops.scope(PROFILE=prof):      # (ops.scope: the switch is set for the block and restored whatever happens inside)
+        for _ in range(reps):
+            trainer._fwd_bwd(im, mk, rects, targets, nb)
+    torch.cuda.synchronize()
+    fam = {}
+    shapes = {}
+    for family, flops, e0, e1, tag, nbytes, issued in prof:
+        if tag is not None:
+            sh = shapes.setdefault((family,) + tuple(tag), [0.0, 0.0, 0])
+            sh[0] += flops; sh[1] += e0.elapsed_time(e1) * 1e-3; sh[2] += 1
+        f = fam.setdefault(family, [0.0, 0.0, 0, 0.0, 0.0])
+        f[4] += issued
+        f[0] += flops
+        f[1] += e0.elapsed_time(e1) * 1e-3
+        f[2] += 1
+        f[3] += nbytes
+    # the same leg with the weight gradients submitted at the END of the backward instead of beside the data-gradient chain: the family
+    # times of kernels that do not share the chip with another stream (the product runs the overlapped form: ops.WGRAD_EVERY)
+    unoverlapped = None
+    if ops.WGRAD_EVERY or ops.BRANCH_BESIDE:
+        prof2 = []
+        with ops.arithmetic(*trainer.arith), ops.scope(PROFILE=prof2, WGRAD_EVERY=0, BRANCH_BESIDE=0):
+            for _ in range(reps):
+                trainer._fwd_bwd(im, mk, rects, targets, nb)
+        torch.cuda.synchronize()
+        f2 = {}
+        for family, flops, e0, e1, tag, nbytes, issued in prof2:
+            f = f2.setdefault(family, [0.0, 0.0, 0])
+            f[0] += flops; f[1] += e0.elapsed_time(e1) * 1e-3; f[2] += 1
+        dense_ = PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
+        unoverlapped = {k: {"tflops": v[0] / v[1] / 1e12, "frac": v[0] / v[1] / 1e12 / dense_, "ms_per_step": v[1] / reps * 1e3,
+                            "avg_launch_us": v[1] / max(v[2], 1) * 1e6} for k, v in f2.items() if v[1] > 0}
+        unoverlapped["note"] = ("the same launches with ops.WGRAD_EVERY = 0 and ops.BRANCH_BESIDE = 0 (weight gradients after the data-gradient chain, shortcut "
+                                "convolutions in line: nothing shares the chip): per-kernel figures without the stretch of running beside another stream -- "
+                                "the step is 0.2-0.3 ms slower that way.  roofline.achieved / frac / families are the launches AS THEY RUN in the product "
+                                "(two streams share the chip during the backbone's backward and at its three shortcut convolutions: every kernel there "
+                                "takes longer, their sum takes less)")
+    if os.environ.get("CDETR_BENCH_SHAPES") and rank == 0:
+        rows = sorted(shapes.items(), key=lambda kv: -kv[1][1])
+        with open(os.environ["CDETR_BENCH_SHAPES"], "w") as f:
+            f.write("family,M,N,K,taps,layout,batch,calls_per_step,us_per_call,ms_per_step,tflops\n")
+            for k, v in rows:
+                f.write(",".join(str(x) for x in k) + f",{v[2] // reps},{v[1] / v[2] * 1e6:.1f},{v[1] / reps * 1e3:.3f},{v[0] / v[1] / 1e12:.1f}\n")
+    bb.set_backward_hook(hook)
+    # HBM traffic per launch: PMC counters need their own rocprofv3 passes (FETCH_SIZE and WRITE_SIZE cannot share one), so the
+    # figures are read from the committed summary of those passes (tools/run_meas.sh -> profiles/r2_traffic.json)
+    tj = None
+    if os.path.exists(TRAFFIC_JSON) and (H, W, a.queries, a.batch, a.precision, a.prior) == (800, 800, 300, 2, "bf16x3", "learned"):
+        with open(TRAFFIC_JSON) as f:
+            tj = json.load(f)
+    kern = {}
+    for k, v in fam.items():
+        if v[1] <= 0:
+            continue
+        tps = (tj or {}).get("families_bytes_per_step", {}).get(k)         # PMC bytes of the family per step (profiles/r2_traffic.json)
+        kern[k] = {"tflops": v[0] / v[1] / 1e12, "mfma_issued_tflops": v[4] / v[1] / 1e12, "mfma_per_product": v[4] / max(v[0], 1.0),
+                   "frac": v[0] / v[1] / 1e12 / (PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS),
+                   "mfma_issue_frac": v[4] / v[1] / 1e12 / (PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS),
+                   "traffic_GBps": (tps / (v[1] / reps) / 1e9) if tps else None,
+                   "ms_per_step": v[1] / reps * 1e3, "launches_per_step": v[2] // reps,
+                   "gflop_per_step": v[0] / reps / 1e9, "algorithmic_bytes_per_launch": v[3] / max(v[2], 1),
+                   "algorithmic_bytes_per_step": v[3] / reps, "traffic_bytes_per_step": tps,
+                   "traffic_bytes_per_launch": (tps / max(v[2] // reps, 1)) if tps else None,     # per host-side launch (a grouped launch = one)
+                   "traffic_over_algorithmic": (tps / (v[3] / reps)) if (tps and v[3]) else None}
+    ig = fam.get("igemm", [0.0, 1.0, 1, 0.0, 1.0])
+    achieved = ig[0] / ig[1] / 1e12
+    # peak for ALGORITHMIC FLOPs of this family = dense bf16 MFMA peak / (bf16 MFMAs issued per algorithmic product, FLOP-weighted
+    # over the family's launches: 3 in the split-bf16 forward, 1 in the plain-bf16 backward) -- so frac = issued MFMA rate / 2500 TF
+    per_product = ig[4] / max(ig[0], 1.0)
+    gflop_img = step_gflop_per_image(H, W, Q)
+    dense = PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
+    total_traffic = (tj or {}).get("total_bytes_per_step")
+    roofline = {"bound": "mfma", "achieved": achieved, "peak": dense, "unit": "TFLOP/s",
+                "bound_note": "priced against the matrix pipe as the contract asks (dense contraction).  What the launches actually run into at these shapes "
+                              "(M = 5000-20000 rows: 1-2.5 tile workgroups per CU) is not the pipe: the long reductions (3x3, K >= 1024) move their operand "
+                              "lines L2 -> LDS at 50-75 GB/s per CU (k-steps of 16 / 24 / 32 KB in 0.38 / 0.54 / 0.73 us whatever the loader, ring depth or "
+                              "arithmetic), the short ones (K <= 512 into N >= 1024) stream 53-120 MB of epilogue operands at 2.3-2.7 TB/s -- HISTORY.md (round 4), "
+                              "profiles/r4_dl_sweep_regstage*.txt, r4_stride_pad.txt, r4_ab_epilogue_touch.txt.  Round 5: a third fewer operand bytes per "
+                              "k-step (3x3 halo resident in LDS), another operand format (interleaved groups), 2-4x the work per barrier and 5 instead of 3 "
+                              "resident workgroups per CU each left these launches where they were: at about one wave per SIMD a workgroup is a latency "
+                              "chain, not a byte stream -- DESIGN.md section 0, profiles/r5_ab_halo_3x3.txt, r5_ab_groups.txt, r5_ab_wgrad.txt",
+                "frac": achieved / dense,
+                "frac_note": "ALGORITHMIC FLOPs (2*M*N*K*taps per launch) of the dominant kernel family / HIP-event time of its launches / the "
+                             "dense MFMA peak of the arithmetic's input type (2500 TF bf16; 157.3 TF for --precision fp32).  The split-bf16 forward "
+                             "issues 3 bf16 MFMAs per algorithmic product, the plain-bf16 backward 1: mfma_issue_frac is the issued-MFMA rate "
+                             "over the same peak (round 2 reported THAT number as frac)",
+                "mfma_per_product": per_product, "mfma_issue_frac": achieved * per_product / dense,
+                "traffic": kern.get("igemm", {}).get("traffic_bytes_per_launch"), "traffic_unit": "bytes/launch",
+                "traffic_source": (tj or {}).get("source"),
+                "algorithmic_bytes_per_launch": ig[3] / max(ig[2], 1),
+                "hbm": ({"bytes_per_step": total_traffic, "achieved_TBps": total_traffic / (ms_per_step * 1e-3) / 1e12,
+                         "frac_of_8TBps": total_traffic / (ms_per_step * 1e-3) / 8e12,
+                         "note": "all kernels of one captured step, FETCH_SIZE (x2, gfx950) + WRITE_SIZE from separate --pmc passes"}
+                        if total_traffic else None),
+                "kernel": "the tile GEMM kernels (igemm_fast_kernel / igemm_dl_kernel: conv fwd / dgrad / linears of > 48 output tiles) -- algorithmic "
+                          "FLOPs 2*M*N*K*taps per launch; the few-row GEMMs (decoder, positional MLPs, heads: launch-latency class, igemm_direct_kernel) "
+                          "are the separate family igemm_fewrow",
+                "avg_launch_us": ig[1] / max(ig[2], 1) * 1e6, "families": kern, "unoverlapped": unoverlapped,
+                "whole_step_tflops": gflop_img * a.batch / ms_per_step, "whole_step_frac": gflop_img * a.batch / ms_per_step / dense,
+                "step_gflop_per_image": gflop_img,
+                "pmc": (tj or {}).get("pmc")}
+    return roofline
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -460,13 +580,17 @@ def main(argv=None):
                          "the bucketed all-reduce between them); auto (default) times 3 steps of each after a short warm-up and keeps "
                          "the faster one.  Both overlap the gradient exchange with the backbone's backward")
     ap.add_argument("--no-graph", action="store_true", help="same as --mode eager")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also measure what takes runs of its own: the roofline legs, the in-line "
+                         "frozen stage and, on one GPU, the other precision, the extra shapes, the inference / stage-1 / real-data legs and "
+                         "the CPU baseline.  Without it the line carries the headline figures only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--precision", choices=list(PRECISIONS), default="bf16x3",
                     help="matrix-core arithmetic of the GEMM kernels: split-bf16 x3 (default, ~5e-6 rel) or fp32 MFMA (exact products)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the short run in the other precision mode")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra shapes (grid-576 queries, 384x576 image)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the inference leg (forward + counting rule, graph replay)")
-    ap.add_argument("--no-real-data", action="store_true", help="skip the graph-cache leg (variable image sizes / target counts)")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the short run in the other precision mode")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra shapes (grid-576 queries, 384x576 image)")
+    ap.add_argument("--no-inference", action="store_true", help="--full: skip the inference leg (forward + counting rule, graph replay)")
+    ap.add_argument("--no-real-data", action="store_true", help="--full: skip the graph-cache leg (variable image sizes / target counts)")
     ap.add_argument("--no-prefetch", action="store_true",
                     help="graph mode: run the frozen stage (stem + layer1) of a batch inside its own step instead of beside the previous step's "
                          "matcher / backward (engine.Trainer: frozen-stage prefetch)")
@@ -590,117 +714,6 @@ def main(argv=None):
     ms_per_step = dt / a.steps * 1e3
     value = a.batch * world * a.steps / dt
 
-    # ---- roofline leg: same fwd+bwd, eager, every matrix-core launch bracketed by HIP events on its own stream
-    import counting_detr_amd.backbone as bb
-    hook = bb._BACKWARD_HOOK
-    bb.set_backward_hook(None)
-    nb = float(sum(len(t_["boxes"]) for t_ in targets))
-    from counting_detr_amd.misc import nested_tensor_from_tensor_list
-    im, mk = nested_tensor_from_tensor_list(images).decompose()
-    reps = 2
-    prof = []
-    with ops.arithmetic(*trainer.arith), ops.scope(PROFILE=prof):      # (ops.scope: the switch is set for the block and restored whatever happens inside)
-        for _ in range(reps):
-            trainer._fwd_bwd(im, mk, rects, targets, nb)
-    torch.cuda.synchronize()
-    fam = {}
-    shapes = {}
-    for family, flops, e0, e1, tag, nbytes, issued in prof:
-        if tag is not None:
-            sh = shapes.setdefault((family,) + tuple(tag), [0.0, 0.0, 0])
-            sh[0] += flops; sh[1] += e0.elapsed_time(e1) * 1e-3; sh[2] += 1
-        f = fam.setdefault(family, [0.0, 0.0, 0, 0.0, 0.0])
-        f[4] += issued
-        f[0] += flops
-        f[1] += e0.elapsed_time(e1) * 1e-3
-        f[2] += 1
-        f[3] += nbytes
-    # the same leg with the weight gradients submitted at the END of the backward instead of beside the data-gradient chain: the family
-    # times of kernels that do not share the chip with another stream (the product runs the overlapped form: ops.WGRAD_EVERY)
-    unoverlapped = None
-    if ops.WGRAD_EVERY or ops.BRANCH_BESIDE:
-        prof2 = []
-        with ops.arithmetic(*trainer.arith), ops.scope(PROFILE=prof2, WGRAD_EVERY=0, BRANCH_BESIDE=0):
-            for _ in range(reps):
-                trainer._fwd_bwd(im, mk, rects, targets, nb)
-        torch.cuda.synchronize()
-        f2 = {}
-        for family, flops, e0, e1, tag, nbytes, issued in prof2:
-            f = f2.setdefault(family, [0.0, 0.0, 0])
-            f[0] += flops; f[1] += e0.elapsed_time(e1) * 1e-3; f[2] += 1
-        dense_ = PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-        unoverlapped = {k: {"tflops": v[0] / v[1] / 1e12, "frac": v[0] / v[1] / 1e12 / dense_, "ms_per_step": v[1] / reps * 1e3,
-                            "avg_launch_us": v[1] / max(v[2], 1) * 1e6} for k, v in f2.items() if v[1] > 0}
-        unoverlapped["note"] = ("the same launches with ops.WGRAD_EVERY = 0 and ops.BRANCH_BESIDE = 0 (weight gradients after the data-gradient chain, shortcut "
-                                "convolutions in line: nothing shares the chip): per-kernel figures without the stretch of running beside another stream -- "
-                                "the step is 0.2-0.3 ms slower that way.  roofline.achieved / frac / families are the launches AS THEY RUN in the product "
-                                "(two streams share the chip during the backbone's backward and at its three shortcut convolutions: every kernel there "
-                                "takes longer, their sum takes less)")
-    if os.environ.get("CDETR_BENCH_SHAPES") and rank == 0:
-        rows = sorted(shapes.items(), key=lambda kv: -kv[1][1])
-        with open(os.environ["CDETR_BENCH_SHAPES"], "w") as f:
-            f.write("family,M,N,K,taps,layout,batch,calls_per_step,us_per_call,ms_per_step,tflops\n")
-            for k, v in rows:
-                f.write(",".join(str(x) for x in k) + f",{v[2] // reps},{v[1] / v[2] * 1e6:.1f},{v[1] / reps * 1e3:.3f},{v[0] / v[1] / 1e12:.1f}\n")
-    bb.set_backward_hook(hook)
-    # HBM traffic per launch: PMC counters need their own rocprofv3 passes (FETCH_SIZE and WRITE_SIZE cannot share one), so the
-    # figures are read from the committed summary of those passes (tools/run_meas.sh -> profiles/r2_traffic.json)
-    tj = None
-    if os.path.exists(TRAFFIC_JSON) and (H, W, a.queries, a.batch, a.precision, a.prior) == (800, 800, 300, 2, "bf16x3", "learned"):
-        with open(TRAFFIC_JSON) as f:
-            tj = json.load(f)
-    kern = {}
-    for k, v in fam.items():
-        if v[1] <= 0:
-            continue
-        tps = (tj or {}).get("families_bytes_per_step", {}).get(k)         # PMC bytes of the family per step (profiles/r2_traffic.json)
-        kern[k] = {"tflops": v[0] / v[1] / 1e12, "mfma_issued_tflops": v[4] / v[1] / 1e12, "mfma_per_product": v[4] / max(v[0], 1.0),
-                   "frac": v[0] / v[1] / 1e12 / (PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS),
-                   "mfma_issue_frac": v[4] / v[1] / 1e12 / (PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS),
-                   "traffic_GBps": (tps / (v[1] / reps) / 1e9) if tps else None,
-                   "ms_per_step": v[1] / reps * 1e3, "launches_per_step": v[2] // reps,
-                   "gflop_per_step": v[0] / reps / 1e9, "algorithmic_bytes_per_launch": v[3] / max(v[2], 1),
-                   "algorithmic_bytes_per_step": v[3] / reps, "traffic_bytes_per_step": tps,
-                   "traffic_bytes_per_launch": (tps / max(v[2] // reps, 1)) if tps else None,     # per host-side launch (a grouped launch = one)
-                   "traffic_over_algorithmic": (tps / (v[3] / reps)) if (tps and v[3]) else None}
-    ig = fam.get("igemm", [0.0, 1.0, 1, 0.0, 1.0])
-    achieved = ig[0] / ig[1] / 1e12
-    # peak for ALGORITHMIC FLOPs of this family = dense bf16 MFMA peak / (bf16 MFMAs issued per algorithmic product, FLOP-weighted
-    # over the family's launches: 3 in the split-bf16 forward, 1 in the plain-bf16 backward) -- so frac = issued MFMA rate / 2500 TF
-    per_product = ig[4] / max(ig[0], 1.0)
-    gflop_img = step_gflop_per_image(H, W, Q)
-    dense = PEAK_FP32_MFMA_TFLOPS if a.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-    total_traffic = (tj or {}).get("total_bytes_per_step")
-    roofline = {"bound": "mfma", "achieved": achieved, "peak": dense, "unit": "TFLOP/s",
-                "bound_note": "priced against the matrix pipe as the contract asks (dense contraction).  What the launches actually run into at these shapes "
-                              "(M = 5000-20000 rows: 1-2.5 tile workgroups per CU) is not the pipe: the long reductions (3x3, K >= 1024) move their operand "
-                              "lines L2 -> LDS at 50-75 GB/s per CU (k-steps of 16 / 24 / 32 KB in 0.38 / 0.54 / 0.73 us whatever the loader, ring depth or "
-                              "arithmetic), the short ones (K <= 512 into N >= 1024) stream 53-120 MB of epilogue operands at 2.3-2.7 TB/s -- HISTORY.md (round 4), "
-                              "profiles/r4_dl_sweep_regstage*.txt, r4_stride_pad.txt, r4_ab_epilogue_touch.txt.  Round 5: a third fewer operand bytes per "
-                              "k-step (3x3 halo resident in LDS), another operand format (interleaved groups), 2-4x the work per barrier and 5 instead of 3 "
-                              "resident workgroups per CU each left these launches where they were: at about one wave per SIMD a workgroup is a latency "
-                              "chain, not a byte stream -- DESIGN.md section 0, profiles/r5_ab_halo_3x3.txt, r5_ab_groups.txt, r5_ab_wgrad.txt",
-                "frac": achieved / dense,
-                "frac_note": "ALGORITHMIC FLOPs (2*M*N*K*taps per launch) of the dominant kernel family / HIP-event time of its launches / the "
-                             "dense MFMA peak of the arithmetic's input type (2500 TF bf16; 157.3 TF for --precision fp32).  The split-bf16 forward "
-                             "issues 3 bf16 MFMAs per algorithmic product, the plain-bf16 backward 1: mfma_issue_frac is the issued-MFMA rate "
-                             "over the same peak (round 2 reported THAT number as frac)",
-                "mfma_per_product": per_product, "mfma_issue_frac": achieved * per_product / dense,
-                "traffic": kern.get("igemm", {}).get("traffic_bytes_per_launch"), "traffic_unit": "bytes/launch",
-                "traffic_source": (tj or {}).get("source"),
-                "algorithmic_bytes_per_launch": ig[3] / max(ig[2], 1),
-                "hbm": ({"bytes_per_step": total_traffic, "achieved_TBps": total_traffic / (ms_per_step * 1e-3) / 1e12,
-                         "frac_of_8TBps": total_traffic / (ms_per_step * 1e-3) / 8e12,
-                         "note": "all kernels of one captured step, FETCH_SIZE (x2, gfx950) + WRITE_SIZE from separate --pmc passes"}
-                        if total_traffic else None),
-                "kernel": "the tile GEMM kernels (igemm_fast_kernel / igemm_dl_kernel: conv fwd / dgrad / linears of > 48 output tiles) -- algorithmic "
-                          "FLOPs 2*M*N*K*taps per launch; the few-row GEMMs (decoder, positional MLPs, heads: launch-latency class, igemm_direct_kernel) "
-                          "are the separate family igemm_fewrow",
-                "avg_launch_us": ig[1] / max(ig[2], 1) * 1e6, "families": kern, "unoverlapped": unoverlapped,
-                "whole_step_tflops": gflop_img * a.batch / ms_per_step, "whole_step_frac": gflop_img * a.batch / ms_per_step / dense,
-                "step_gflop_per_image": gflop_img,
-                "pmc": (tj or {}).get("pmc")}
-
     res = {"metric": "images/sec FSCD-147 2nd-stage train step", "value": value, "unit": "images/s", "n_gpus": world,
            "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": dtype_string(a.precision),
@@ -720,8 +733,12 @@ def main(argv=None):
            "scaling_note": ("measured on %d ranks" % world) if world > 1 else
                            "single-GPU line; no N > 1 scaling curve has been measured for this repo yet (one-GPU leases only: the driver's "
                            "SCALE run is the first RCCL execution of the N > 1 path)",
-           "roofline": roofline}
-    if pipelined and mode != "eager":
+           }
+    if a.full:
+        res["roofline"] = roofline_leg(trainer, images, rects, targets, a, Q, ms_per_step, rank)
+    elif os.environ.get("CDETR_BENCH_SHAPES") and rank == 0:
+        print("[bench] CDETR_BENCH_SHAPES: the per-shape table comes from the roofline leg, which runs with --full only", file=sys.stderr, flush=True)
+    if a.full and pipelined and mode != "eager":
         # the same captured step with its frozen stage in line (no look-ahead): short run on the same box, for transparency
         for _ in range(3):
             trainer.replay()
@@ -746,7 +763,7 @@ def main(argv=None):
                                        "backend": "gloo (rehearsal)" if share else "nccl (RCCL over xGMI)",
                                        "note": "time the compute stream waits for the last gradient bucket before clip + AdamW "
                                                "(HIP events on the compute and exchange streams); 0 = fully hidden behind backward"}
-    if world == 1 and not a.no_alt:
+    if a.full and world == 1 and not a.no_alt:
         # the same step in the other arithmetic mode (short run, same launch mode), for transparency
         alt = "fp32" if a.precision != "fp32" else "bf16x3"
         own, trainer.arith = trainer.arith, (PRECISIONS[alt], trainer.arith[1])      # (the trainer computes in ITS arithmetic, not the module default)
@@ -765,7 +782,7 @@ def main(argv=None):
         dta = (time.perf_counter() - t1) / 5
         res["alt_precision"] = {"precision": alt, "value": a.batch / dta, "unit": "images/s", "ms_per_step": dta * 1e3, "steps": 5}
         trainer.arith = own
-    if world == 1 and not a.no_extra:
+    if a.full and world == 1 and not a.no_extra:
         del trainer
         torch.cuda.empty_cache()
         res["extra_shapes"] = [
@@ -780,12 +797,12 @@ def main(argv=None):
             # BASELINE configs[3] (FSCD-LVIS 2nd stage) at the largest image its reader feeds (L2/data/fscd_lvis.py:66-91: floor-32 of the image,
             # longest side up to 1333): feature map 50 x 84 -- wider than one 64-key tile (round 6: rcda_fwd2_kernel<4, 6>, dV key-column chunks)
             extra_shape(dev, 800, 1333, 300, "learned", Ts, a.batch, a.precision)]
-    if world == 1 and not a.no_inference:
+    if a.full and world == 1 and not a.no_inference:
         res["inference"] = inference_leg(dev, [(800, 800), (384, 576), (800, 800, 8), (384, 576, 16)], a.batch, a.precision)
         res["stage1_pseudo_labels"] = stage1_leg(dev, a.precision)
-    if world == 1 and not a.no_real_data:
+    if a.full and world == 1 and not a.no_real_data:
         res["real_data_loop"] = real_data_leg(dev, a.precision, a.batch)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(a.batch, H, W, Ts)
     if rank == 0:
         print(json.dumps(res), flush=True)

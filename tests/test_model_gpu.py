@@ -401,7 +401,8 @@ def test_bench_self_launches_two_ranks_rehearsal():
     """`python bench.py --gpus 2` with no launcher around it spawns the two ranks itself (torch.distributed.run, 127.0.0.1) and
     prints ONE line for the whole job.  On this one-GPU box the ranks share the device and gloo carries the collectives
     (CDETR_BENCH_SHARE_GPU=1 -- the line is tagged as a rehearsal); the control flow -- self-launch, replica sync, five-graph
-    replay with the bucketed exchange between the graphs, exposed all-reduce time -- is the one the 8-GPU run takes."""
+    replay with the bucketed exchange between the graphs, exposed all-reduce time, and with --full the roofline leg -- is the one
+    the 8-GPU run takes."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CDETR_BENCH_SHARE_GPU="1")
@@ -409,7 +410,7 @@ def test_bench_self_launches_two_ranks_rehearsal():
         env.pop(k, None)
     for mode in ("auto", "graph", "eager"):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "256", "256",
-                            "--queries", "100", "--mode", mode, "--no-cpu-baseline", "--no-alt", "--no-extra"],
+                            "--queries", "100", "--mode", mode, "--full", "--no-cpu-baseline", "--no-alt", "--no-extra"],
                            env=env, cwd=root, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -455,6 +456,28 @@ def test_bench_dump_outputs_of_the_timed_step(tmp_path):
             np.testing.assert_allclose(b, a, rtol=1e-4, atol=1e-5 * float(np.abs(a).max()), err_msg=k)
         else:
             np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-7, err_msg=k)
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """`bench.py` without --full: set-up, warm-up, the timed steps and ONE line with the headline figures; the legs that take runs of
+    their own (roofline, in-line frozen stage, other precision, extra shapes, inference, stage 1, real-data loop, CPU baseline) run with
+    --full only."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "256", "256",
+                        "--queries", "100", "--mode", "graph"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "step_ms"} <= set(r)
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["step_ms"]["n"] == 2 and r["value"] > 0 and r["config"]["graph"]
+    full_only = {"roofline", "frozen_stage_prefetch", "alt_precision", "extra_shapes", "inference", "stage1_pseudo_labels", "real_data_loop",
+                 "cpu_baseline"}
+    assert not full_only & set(r), sorted(r)
 
 
 def test_fscd_lvis_train_epoch_and_infer(tmp_path):

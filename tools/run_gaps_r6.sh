@@ -1,6 +1,6 @@
 # main-queue idle gaps of a PIPELINED captured step (tools/step_gaps.py): with / without the event between F and B
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-F="--no-cpu-baseline --no-alt --no-extra --no-inference --no-real-data"
+F="--full --no-cpu-baseline --no-alt --no-extra --no-inference --no-real-data"
 for cfg in "CDETR_PF_TIMEOUT_US=4000" "CDETR_NO_EVF=1 CDETR_PF_TIMEOUT_US=4000"; do
   rm -rf /tmp/prof_g; env $cfg timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_g -- python bench.py --mode graph --steps 6 --warmup 2 $F > /tmp/g.log 2>&1
   f=$(find /tmp/prof_g -name "*kernel_trace.csv")

@@ -5,10 +5,10 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/r6meas
 mkdir -p $O
-timeout 900 python bench.py > $O/bench_full.log 2> $O/bench_full.err
+timeout 900 python bench.py --full > $O/bench_full.log 2> $O/bench_full.err
 tail -1 $O/bench_full.log | cut -c1-300
 for s in "CDETR_GRAPH_LAYOUT=single" "CDETR_GRAPH_LAYOUT=chain"; do echo "== $s"; env $s python tools/host_cost.py 2>&1 | tail -3; done > $O/host_cost.txt 2>&1
-F="--no-cpu-baseline --no-alt --no-extra --no-inference --no-real-data"
+F="--full --no-cpu-baseline --no-alt --no-extra --no-inference --no-real-data"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k -- python bench.py --mode graph --steps 20 --warmup 5 $F > $O/bench_prof.log 2>&1
 find /tmp/prof_k -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 python tools/kernel_stats.py $O/bench_kernel_stats.csv 70 > $O/kernel_summary.txt 2>&1

@@ -11,7 +11,7 @@ with open(sys.argv[1]) as f:
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "0")))
 rows.sort()
 # a step = the kernels between two adamw_finish launches; which one: argv[3] counts from the end (default 2: the last but one full step --
-# bench.py's timed (pipelined) steps come before its in-line comparison steps, pass a larger number to look at those)
+# bench.py --full's timed (pipelined) steps come before its in-line comparison steps, pass a larger number to look at those)
 ends = [i for i, r in enumerate(rows) if "adamw_finish" in r[2]]
 back = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 e0 = ends[-back]
