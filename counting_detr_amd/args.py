@@ -19,7 +19,7 @@ def get_args_parser():
     p.add_argument("--lr_drop", default=20, type=int)
     p.add_argument("--lr_drop_epochs", default=None, type=int, nargs="+")
     p.add_argument("--clip_max_norm", default=0.1, type=float)
-    p.add_argument("--sgd", action="store_true")
+    p.add_argument("--sgd", action="store_true", help="torch.optim.SGD(momentum=0.9) over the same lr groups instead of AdamW (A2/main.py:185-186)")
     p.add_argument("--frozen_weights", type=str, default=None)
     p.add_argument("--backbone", default="resnet50", type=str)
     p.add_argument("--dilation", default=True, type=lambda s: str(s).lower() not in ("0", "false", "no"))

@@ -5,6 +5,8 @@
 //                     / moment arenas in ONE pass: 4 reads + 3 writes per element instead of ~12 torch passes
 //                     (A2/engine.py:54-57, A2/main.py:186: torch.optim.AdamW defaults betas (0.9, 0.999), eps 1e-8).
 //                     Step count, learning-rate scale and the clip coefficient live in device memory (graph replay safe).
+// cdetr_sgd_step    : the same clip + torch.optim.SGD (momentum, dampening 0, coupled L2 weight decay) over the flat parameter /
+//                     gradient / momentum-buffer arenas in ONE pass: 3 reads + 2 writes per element (A2/main.py:185-186, --sgd).
 // cdetr_relu_mask   : dz = (y > 0) ? dy * scale : 0   (ReLU backward for the linear layers, one pass).
 #include "../../include/cdetr_hip.h"
 #include "common.h"
@@ -43,6 +45,31 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restric
     if (threadIdx.x == 0) out[0] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
+// The preamble of both fused updates.  clip_coef: the clip coefficient times grad_div (= 1 / world_size, which folds the data-parallel
+// average into the same pass), or false when the norm of the averaged gradient is non-finite (NaN / Inf loss, A2/engine.py:44-49): that
+// must reach neither the parameters nor the optimizer state, so the whole update is skipped -- a grid-uniform branch, every block reads
+// the same sumsq[0] -- and adamw_finish_kernel latches the event in state[3] for the host to read when it next looks.
+__device__ __forceinline__ bool clip_coef(const float* __restrict__ sumsq, float max_norm, float grad_div, float& coef) {
+    const float total_norm = sqrtf(sumsq[0]) * grad_div;
+    if (!(fabsf(total_norm) <= 3.0e38f)) return false;
+    coef = 1.f;
+    if (max_norm > 0.f) coef = fminf(max_norm / (total_norm + 1e-6f), 1.f);
+    coef *= grad_div;
+    return true;
+}
+
+// Base learning rate of float4 i / of element i.  lr == NULL: two learning rates split at element lr_split (the arena is ordered
+// [everything else | backbone], A2/main.py:157-183): one 150 MB stream less than the per-element table (lr_split is a multiple of 4 or
+// the table is used)
+__device__ __forceinline__ float4 lr4_at(const float* __restrict__ lr, long i, float lr0, float lr1, long lr_split) {
+    if (lr) return reinterpret_cast<const float4*>(lr)[i];
+    const float l = (4 * i < lr_split) ? lr0 : lr1;
+    return make_float4(l, l, l, l);
+}
+__device__ __forceinline__ float lr_at(const float* __restrict__ lr, long i, float lr0, float lr1, long lr_split) {
+    return lr ? lr[i] : (i < lr_split ? lr0 : lr1);
+}
+
 // state[0] = step count t (float, incremented here by block 0), state[1] = lr scale (StepLR factor),
 // sumsq[0] = sum of squares of the gradient (from sumsq_kernel); outputs total_norm to state[2].
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -52,13 +79,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     long lr_split) {
     const float t = state[0] + 1.f;
     const float lr_scale = state[1];
-    const float total_norm = sqrtf(sumsq[0]) * grad_div;
-    // a non-finite gradient (NaN / Inf loss, A2/engine.py:44-49) must not reach the parameters or the moments: the whole update is
-    // skipped (grid-uniform branch) and adamw_finish_kernel latches the event in state[3] for the host to read when it next looks
-    if (!(fabsf(total_norm) <= 3.0e38f)) return;
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (total_norm + 1e-6f), 1.f);
-    coef *= grad_div;                      // grad_div = 1 / world_size folds the data-parallel average into the same pass
+    float coef;
+    if (!clip_coef(sumsq, max_norm, grad_div, coef)) return;
     const float bc1 = 1.f - powf(beta1, t);
     const float bc2 = 1.f - powf(beta2, t);
     const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
@@ -67,7 +89,6 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const float4* g4 = reinterpret_cast<const float4*>(g);
     float4* m4 = reinterpret_cast<float4*>(m);
     float4* v4 = reinterpret_cast<float4*>(v);
-    const float4* l4 = reinterpret_cast<const float4*>(lr);
     auto upd = [&](float& pp, float gg, float& mm, float& vv, float l) {
         gg *= coef;
         l *= lr_scale;
@@ -77,14 +98,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
         pp -= (l / bc1) * (mm / denom);
     };
-    // lr == NULL: two learning rates split at element lr_split (the arena is ordered [everything else | backbone], A2/main.py:157-183):
-    // one 150 MB stream less than the per-element table (lr_split is a multiple of 4 or the table is used)
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         float4 pp = p4[i], mm = m4[i], vv = v4[i];
         const float4 gg = g4[i];
-        float4 ll;
-        if (lr) ll = l4[i];
-        else { const float l = (4 * i < lr_split) ? lr0 : lr1; ll = make_float4(l, l, l, l); }
+        const float4 ll = lr4_at(lr, i, lr0, lr1, lr_split);
         upd(pp.x, gg.x, mm.x, vv.x, ll.x);
         upd(pp.y, gg.y, mm.y, vv.y, ll.y);
         upd(pp.z, gg.z, mm.z, vv.z, ll.z);
@@ -92,9 +109,42 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
     if (blockIdx.x == 0)
-        for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i], lr ? lr[i] : (i < lr_split ? lr0 : lr1));
+        for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i], lr_at(lr, i, lr0, lr1, lr_split));
     // every block has read state[0] / sumsq before block 0 writes them only if ... they are written by a SEPARATE tiny
     // kernel (adamw_finish) launched after this one -- see cdetr_adamw_step.
+}
+
+// torch.optim.SGD(momentum, dampening 0, nesterov False, weight_decay) after clip_grad_norm_: d = g coef + wd p; buf = momentum buf + d;
+// p -= lr buf.  A zero buffer on the first step gives buf = d, torch's clone rule.  Same state / lr / skip semantics as adamw_kernel,
+// and the same finish kernel after it (state[0] counts steps, though SGD itself does not read it).
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  const float* __restrict__ lr, long n, const float* __restrict__ sumsq,
+                                                  const float* __restrict__ state, float max_norm, float momentum, float wd, float grad_div,
+                                                  float lr0, float lr1, long lr_split) {
+    const float lr_scale = state[1];
+    float coef;
+    if (!clip_coef(sumsq, max_norm, grad_div, coef)) return;
+    const long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+    auto upd = [&](float& pp, float gg, float& bb, float l) {
+        const float d = gg * coef + wd * pp;
+        bb = momentum * bb + d;
+        pp -= (l * lr_scale) * bb;
+    };
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pp = p4[i], bb = b4[i];
+        const float4 gg = g4[i];
+        const float4 ll = lr4_at(lr, i, lr0, lr1, lr_split);
+        upd(pp.x, gg.x, bb.x, ll.x);
+        upd(pp.y, gg.y, bb.y, ll.y);
+        upd(pp.z, gg.z, bb.z, ll.z);
+        upd(pp.w, gg.w, bb.w, ll.w);
+        p4[i] = pp; b4[i] = bb;
+    }
+    if (blockIdx.x == 0)
+        for (long i = (n4 << 2) + threadIdx.x; i < n; i += 256) upd(p[i], g[i], buf[i], lr_at(lr, i, lr0, lr1, lr_split));
 }
 
 __global__ void adamw_finish_kernel(const float* __restrict__ sumsq, float* __restrict__ state, float grad_div) {
@@ -592,6 +642,20 @@ extern "C" int cdetr_adamw_step2(float* p, const float* g, float* m, float* v, c
                        eps, weight_decay, grad_div, lr0, lr1, (long)lr_split);
     hipLaunchKernelGGL(adamw_finish_kernel, dim3(1), dim3(1), 0, st, sumsq, state, grad_div);
     return cdetr_launch_status("cdetr_adamw_step2");
+}
+
+extern "C" int cdetr_sgd_step(float* p, const float* g, float* buf, const float* lr, float lr0, float lr1, int64_t lr_split, int64_t n,
+                              const float* sumsq, float* state, float max_norm, float momentum, float weight_decay, float grad_div,
+                              void* stream) {
+    CDETR_CHECK_ARG(p && g && buf && sumsq && state && n >= 0, "cdetr_sgd_step: null pointer");
+    CDETR_CHECK_ARG(lr || (lr_split >= 0 && (lr_split & 3) == 0), "cdetr_sgd_step: without a per-element table lr_split must be a multiple of 4");
+    CDETR_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf) |
+                      reinterpret_cast<uintptr_t>(lr)) & 15) == 0, "cdetr_sgd_step: arenas must be 16-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, st, p, g, buf, lr, (long)n, sumsq, state, max_norm, momentum,
+                       weight_decay, grad_div, lr0, lr1, (long)lr_split);
+    hipLaunchKernelGGL(adamw_finish_kernel, dim3(1), dim3(1), 0, st, sumsq, state, grad_div);
+    return cdetr_launch_status("cdetr_sgd_step");
 }
 
 extern "C" int cdetr_adamw_step(float* p, const float* g, float* m, float* v, const float* lr, int64_t n, const float* sumsq,

@@ -3,7 +3,8 @@ A2/infer.py:27-122, re-designed for one-process-per-GPU data parallelism on MI35
 
   * all trainable parameters live in ONE flat fp32 arena (views keep the reference's shapes / state-dict keys), their
     gradients in a second arena that the weight-gradient kernels accumulate into directly; clip_grad_norm_(0.1) and AdamW
-    (A2/main.py:157-189: lr 1e-4, "backbone" 1e-5, wd 1e-4) are a handful of flat ops instead of ~250 per-tensor ones;
+    (A2/main.py:157-189: lr 1e-4, "backbone" 1e-5, wd 1e-4; SGD with momentum 0.9 under --sgd) are a handful of flat ops instead
+    of ~250 per-tensor ones;
   * the arena is ordered [transformer+proj | layer4 | layer3 | layer2] = the order gradients become final in backward, so
     the data-parallel all-reduce (RCCL over xGMI) runs as 4 large buckets on a side stream, each launched the moment its
     segment is final and overlapped with the remaining backbone backward;
@@ -324,6 +325,9 @@ class Trainer:
         self.device = torch.device(device or args.device)
         self.max_norm = args.clip_max_norm
         self.betas, self.eps, self.wd = (0.9, 0.999), 1e-8, args.weight_decay
+        # --sgd: torch.optim.SGD(momentum=0.9) over the same three lr groups, StepLR and clip instead of AdamW (A2/main.py:185-188)
+        self.sgd = bool(getattr(args, "sgd", False))
+        self.momentum = 0.9
         self.unused_prefixes = tuple(self.unused_prefixes) + model_unused_prefixes(model)
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and not n.startswith(self.unused_prefixes)]
         for n, p in model.named_parameters():
@@ -335,8 +339,12 @@ class Trainer:
         total = sum(sizes)
         self.flat_p = torch.zeros(total, device=self.device, dtype=torch.float32)
         self.flat_g = torch.zeros(total, device=self.device, dtype=torch.float32)
-        self.exp_avg = torch.zeros_like(self.flat_p)
-        self.exp_avg_sq = torch.zeros_like(self.flat_p)
+        if self.sgd:                            # one state arena: SGD's momentum buffer
+            self.momentum_buffer = torch.zeros_like(self.flat_p)
+            self.exp_avg = self.exp_avg_sq = None
+        else:
+            self.exp_avg = torch.zeros_like(self.flat_p)
+            self.exp_avg_sq = torch.zeros_like(self.flat_p)
         self.lr_vec = torch.zeros(total, device=self.device, dtype=torch.float32)   # per-element base lr
         self.seg_bounds = [0, 0, 0, 0, 0]
         self.offsets = {}
@@ -469,18 +477,27 @@ class Trainer:
         self.exchange.segment_done(seg, also=ops.wgrad_side_stream() if ops._WG_INFLIGHT else None)
 
     def _finish_allreduce(self):
-        self.exchange.finish()      # the 1/world average is folded into cdetr_adamw_step (grad_div)
+        self.exchange.finish()      # the 1/world average is folded into cdetr_adamw_step / cdetr_sgd_step (grad_div)
 
-    # ------------------------------------------------------------------ optimizer (flat clip + AdamW)
+    # ------------------------------------------------------------------ optimizer (flat clip + AdamW, or + SGD with --sgd)
+    @property
+    def optimizer_name(self):
+        return "SGD" if self.sgd else "AdamW"
+
     def _optimizer_step(self):
-        """clip_grad_norm_(max_norm) + AdamW over the flat arenas: one reduction pass + one fused update pass
-        (cdetr_sumsq / cdetr_adamw_step); step count, StepLR factor and the norm stay on the device."""
+        """clip_grad_norm_(max_norm) + AdamW (or SGD) over the flat arenas: one reduction pass + one fused update pass
+        (cdetr_sumsq / cdetr_adamw_step2 or cdetr_sgd_step); step count, StepLR factor and the norm stay on the device."""
         from . import _ffi
         n = self.flat_p.numel()
         b1, b2 = self.betas
         st = _ffi.stream_ptr()
         _ffi.check(_ffi.lib().cdetr_sumsq(self.flat_g.data_ptr(), n, self.sumsq.data_ptr(), self.sumsq_ws.data_ptr(), st), "cdetr_sumsq")
         lr_tab, lr0, lr1, split = (None, *self._lr_two) if self._lr_two is not None else (self.lr_vec.data_ptr(), 0.0, 0.0, 0)
+        if self.sgd:
+            _ffi.check(_ffi.lib().cdetr_sgd_step(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.momentum_buffer.data_ptr(), lr_tab, lr0,
+                                                 lr1, split, n, self.sumsq.data_ptr(), self.opt_state.data_ptr(), float(self.max_norm),
+                                                 self.momentum, self.wd, 1.0 / get_world_size(), st), "cdetr_sgd_step")
+            return self.opt_state[2]
         _ffi.check(_ffi.lib().cdetr_adamw_step2(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(),
                                                 self.exp_avg_sq.data_ptr(), lr_tab, lr0, lr1, split, n, self.sumsq.data_ptr(),
                                                 self.opt_state.data_ptr(), float(self.max_norm), b1, b2, self.eps, self.wd,
@@ -501,7 +518,10 @@ class Trainer:
         """The checkpoint's "optimizer" entry in torch.optim.AdamW's own state_dict layout (what the reference writes,
         A2/main.py:228-231): {"state": {index: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]} with the reference's
         three groups and parameter numbering; parameters that never receive a gradient (`input_proj.*`) have no state entry,
-        as in torch.  Tools written against the reference's checkpoints read it unchanged; `load_state_dict` reads it back."""
+        as in torch.  Tools written against the reference's checkpoints read it unchanged; `load_state_dict` reads it back.
+        With --sgd: torch.optim.SGD's layout, {"state": {index: {"momentum_buffer"}}, ...} (`_sgd_state_dict`)."""
+        if self.sgd:
+            return self._sgd_state_dict()
         groups, lrs = self._torch_param_order()
         params = dict(self.model.named_parameters())
         factor = float(self.opt_state[1])
@@ -523,6 +543,42 @@ class Trainer:
                         "initial_lr": lr, "params": ids})
         return {"state": state, "param_groups": pgs}
 
+    def _sgd_state_dict(self):
+        """torch.optim.SGD(momentum=0.9)'s state_dict: the same groups and numbering as the AdamW layout, one "momentum_buffer" per
+        parameter that has taken a step (none before the first step, none for parameters without a gradient -- torch's rules)."""
+        groups, lrs = self._torch_param_order()
+        params = dict(self.model.named_parameters())
+        factor = float(self.opt_state[1])
+        stepped = float(self.opt_state[0]) > 0
+        state, pgs, idx = {}, [], 0
+        b_cpu = self.momentum_buffer.detach().cpu()
+        for names, lr in zip(groups, lrs):
+            ids = []
+            for n in names:
+                if n in self.offsets and stepped:
+                    off, sz = self.offsets[n]
+                    state[idx] = {"momentum_buffer": self._view_like(b_cpu[off:off + sz], params[n]).clone()}
+                ids.append(idx)
+                idx += 1
+            pgs.append({"lr": lr * factor, "momentum": self.momentum, "dampening": 0, "weight_decay": self.wd, "nesterov": False,
+                        "maximize": False, "foreach": None, "differentiable": False, "fused": None, "initial_lr": lr, "params": ids})
+        return {"state": state, "param_groups": pgs}
+
+    @staticmethod
+    def _optimizer_of(sd):
+        """Which optimizer wrote a checkpoint's "optimizer" entry: "SGD", "AdamW" or None (no state and no telling hyper-parameters)."""
+        for st in (sd["state"].values() if isinstance(sd.get("state"), dict) else ()):
+            if "momentum_buffer" in st:
+                return "SGD"
+            if "exp_avg" in st:
+                return "AdamW"
+        pg = sd.get("param_groups") or [{}]
+        if "momentum" in pg[0]:
+            return "SGD"
+        if "betas" in pg[0] or "exp_avg" in sd:
+            return "AdamW"
+        return None
+
     def lr_scheduler_state_dict(self):
         """torch.optim.lr_scheduler.StepLR.state_dict() of the reference's scheduler (A2/main.py:189,232)."""
         _, lrs = self._torch_param_order()
@@ -532,8 +588,16 @@ class Trainer:
 
     def load_state_dict(self, sd, lr_scheduler=None):
         """Restore moments / step count from a checkpoint's "optimizer" entry (torch AdamW layout, from this trainer or from the
-        reference) and the epoch / StepLR factor from its "lr_scheduler" entry."""
-        if "param_groups" in sd:
+        reference) and the epoch / StepLR factor from its "lr_scheduler" entry.  With --sgd: the momentum buffers of torch SGD's layout
+        (this trainer's, or the reference's --sgd checkpoints).  The state of the other optimizer raises."""
+        kind = self._optimizer_of(sd)
+        if kind is not None and kind != self.optimizer_name:
+            raise RuntimeError(f"optimizer state was written by {kind}, this trainer runs {self.optimizer_name}"
+                               f"{' (--sgd)' if self.sgd else ' (no --sgd)'}: resume from the weights only (--resume without --resume_optimizer "
+                               "or --auto_resume) or match --sgd to the checkpoint")
+        if self.sgd:
+            self._load_sgd_state(sd)
+        elif "param_groups" in sd:
             groups, _ = self._torch_param_order()
             order = [n for g in groups for n in g]
             ids = [i for g in sd["param_groups"] for i in g["params"]]
@@ -565,9 +629,30 @@ class Trainer:
         self.opt_state[1] = 0.1 ** (self.epoch // self.args.lr_drop)
         self.opt_state[3] = 0.0
 
+    def _load_sgd_state(self, sd):
+        """torch.optim.SGD's layout (any torch version: only "params" and "momentum_buffer" are read).  torch's SGD keeps no step count:
+        loaded buffers count as one step taken (the count only decides whether `state_dict` writes state; SGD's update does not read it)."""
+        groups, _ = self._torch_param_order()
+        order = [n for g in groups for n in g]
+        ids = [i for g in sd["param_groups"] for i in g["params"]]
+        if len(ids) != len(order):
+            raise RuntimeError(f"optimizer state holds {len(ids)} parameters, this model's optimizer has {len(order)}: the "
+                               "checkpoint comes from another model (pass weights only: drop --resume_optimizer)")
+        params = dict(self.model.named_parameters())
+        self.momentum_buffer.zero_()
+        stepped = False
+        for i, n in zip(ids, order):
+            st = sd["state"].get(i)
+            if st is None or n not in self.offsets or st.get("momentum_buffer") is None:
+                continue
+            off, sz = self.offsets[n]
+            self._view_like(self.momentum_buffer[off:off + sz], params[n]).copy_(st["momentum_buffer"])
+            stepped = True
+        self.opt_state[0] = 1.0 if stepped else 0.0
+
     def nonfinite_steps(self, clear=True):
         """Number of steps whose gradient norm was NaN / Inf since the last call (host sync).  Such a step leaves parameters,
-        moments and step count untouched (cdetr_adamw_step), so nothing is polluted before the host notices."""
+        moments (momentum buffer) and step count untouched (cdetr_adamw_step / cdetr_sgd_step), so nothing is polluted before the host notices."""
         n = int(self.opt_state[3])
         if clear and n:
             self.opt_state[3] = 0.0

@@ -205,6 +205,15 @@ int cdetr_adamw_step(float* p, const float* g, float* m, float* v, const float* 
 int cdetr_adamw_step2(float* p, const float* g, float* m, float* v, const float* lr, float lr0, float lr1, int64_t lr_split, int64_t n,
                       const float* sumsq, float* state, float max_norm, float beta1, float beta2, float eps, float weight_decay,
                       float grad_div, void* stream);
+/* cdetr_sgd_step: torch.optim.SGD(momentum, dampening 0, no Nesterov, coupled L2 weight decay) after the same clip, in one pass over
+ *                 p, g and the momentum buffer buf (A2/main.py:185-186, --sgd):
+ *                 g' = g * grad_div; coef = min(max_norm / (||g'|| + 1e-6), 1) (max_norm <= 0: no clip);
+ *                 d = g' coef + weight_decay p; buf = momentum buf + d; p -= lr buf,  lr = (lr ? lr[i] : i < lr_split ? lr0 : lr1) * state[1].
+ *                 A zero buf before the first step gives buf = d (torch's clone rule).  lr / lr_split and state[4] as in
+ *                 cdetr_adamw_step2: [0] step count, [1] lr scale, [2] <- ||g'||, [3] += 1 when ||g'|| is NaN / Inf (p and buf
+ *                 unchanged, step count too).                                                                                    */
+int cdetr_sgd_step(float* p, const float* g, float* buf, const float* lr, float lr0, float lr1, int64_t lr_split, int64_t n,
+                   const float* sumsq, float* state, float max_norm, float momentum, float weight_decay, float grad_div, void* stream);
 /* dz[i] = y[i] > 0 ? dy[i] * scale : 0      (ReLU backward of the fused linear+ReLU layers) */
 int cdetr_relu_mask(const float* y, const float* dy, float* dz, int64_t n, float scale, void* stream);
 /* the same, also writing a bf16 twin of dz (dz16 may be NULL) */

@@ -1,6 +1,6 @@
 """main.py -- CLI of the reference's 2nd-stage trainer (A2/main.py:17-258) on the MI355X path.
 
-Same flags, same driver behaviour: build_model -> 3 lr groups / AdamW / StepLR(lr_drop) -> optional --resume (model
+Same flags, same driver behaviour: build_model -> 3 lr groups / AdamW (SGD, momentum 0.9, with --sgd) / StepLR(lr_drop) -> optional --resume (model
 weights only, keys filtered like A2/main.py:195-209) -> per epoch train_one_epoch, scheduler step, checkpoint
 {"model","optimizer","lr_scheduler","epoch","args"} to <output_dir>/detr_retrain.pth (+ numbered copies), JSON log line.
 Differences: any number of images per GPU (--images_per_gpu), data-parallel over the GPUs of a node under torchrun
@@ -72,7 +72,10 @@ def main(args):
     if args.resume:                                                     # A2/main.py:195-209
         checkpoint, _, _ = ckpt_io.resume_model(model, args.resume, skip_mismatch=args.resume_skip_mismatch)
 
-    trainer = Trainer(model, criterion, args, device=device, precision_bwd=bwd_precision)           # 3 lr groups + flat AdamW (A2/main.py:157-189); syncs replicas; owns its arithmetic
+    trainer = Trainer(model, criterion, args, device=device, precision_bwd=bwd_precision)           # 3 lr groups + flat AdamW or --sgd SGD (A2/main.py:157-189); syncs replicas; owns its arithmetic
+    if utils.is_main_process():
+        print(f"optimizer: {trainer.optimizer_name}" + (" (momentum 0.9)" if trainer.sgd else "") + f", lr {args.lr}, backbone lr {args.lr_backbone}, "
+              f"weight decay {args.weight_decay}, clip {args.clip_max_norm}")
     if checkpoint is not None and (args.resume_optimizer or args.auto_resume) and checkpoint.get("optimizer"):
         # opt-in (the reference loads weights only and starts at --start_epoch, A2/main.py:195-209): continue an interrupted run
         trainer.load_state_dict(checkpoint["optimizer"], checkpoint.get("lr_scheduler"))
