@@ -5,6 +5,10 @@
 //                     / moment arenas in ONE pass: 4 reads + 3 writes per element instead of ~12 torch passes
 //                     (A2/engine.py:54-57, A2/main.py:186: torch.optim.AdamW defaults betas (0.9, 0.999), eps 1e-8).
 //                     Step count, learning-rate scale and the clip coefficient live in device memory (graph replay safe).
+//                     The step count is a float: exact up to 2^24 steps, far beyond any run of this project.
+// cdetr_adamw_step2 : the same kernel with the learning rates as (lr0, lr1, lr_split) or as the per-element table; this is the entry
+//                     point the product calls (engine.Trainer._optimizer_step).  cdetr_adamw_step (table only) stays exported for the
+//                     ABI.  Both are held to torch.optim.AdamW by tests/test_adamw_kernel_gpu.py.
 // cdetr_sgd_step    : the same clip + torch.optim.SGD (momentum, dampening 0, coupled L2 weight decay) over the flat parameter /
 //                     gradient / momentum-buffer arenas in ONE pass: 3 reads + 2 writes per element (A2/main.py:185-186, --sgd).
 // cdetr_relu_mask   : dz = (y > 0) ? dy * scale : 0   (ReLU backward for the linear layers, one pass).

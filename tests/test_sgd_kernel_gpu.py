@@ -4,42 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+from optimizer_arenas import DEV, Arenas, g
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-class Arenas:
-    """p, g, buf (+ the optional lr table) on the device, the state block [step, lr scale, norm, skipped] and the sumsq workspace."""
-
-    def __init__(self, n, seed=0, lr_table=None, lr0=0.0, lr1=0.0, split=0):
-        self.n = n
-        self.p = torch.randn(n, generator=g(seed)).to(DEV)
-        self.g = (torch.randn(n, generator=g(seed + 1)) * 0.05).to(DEV)
-        self.buf = torch.zeros(n, device=DEV)
-        self.lr = None if lr_table is None else lr_table.to(DEV)
-        self.lr0, self.lr1, self.split = lr0, lr1, split
-        self.state = torch.tensor([0.0, 1.0, 0.0, 0.0], device=DEV)
-        self.sumsq = torch.zeros(1, device=DEV)
-        self.ws = torch.zeros(2048, device=DEV)
-
-    def base_lr(self):
-        if self.lr is not None:
-            return self.lr.double().cpu()
-        i = torch.arange(self.n)
-        return torch.where(i < self.split, torch.tensor(self.lr0, dtype=torch.float64), torch.tensor(self.lr1, dtype=torch.float64))
-
-    def step(self, max_norm, momentum, wd, grad_div=1.0):
-        from counting_detr_amd import _ffi
-        L, st = _ffi.lib(), _ffi.stream_ptr()
-        _ffi.check(L.cdetr_sumsq(self.g.data_ptr(), self.n, self.sumsq.data_ptr(), self.ws.data_ptr(), st), "cdetr_sumsq")
-        _ffi.check(L.cdetr_sgd_step(self.p.data_ptr(), self.g.data_ptr(), self.buf.data_ptr(), None if self.lr is None else self.lr.data_ptr(),
-                                    self.lr0, self.lr1, self.split, self.n, self.sumsq.data_ptr(), self.state.data_ptr(), max_norm, momentum,
-                                    wd, grad_div, st), "cdetr_sgd_step")
-        torch.cuda.synchronize()
 
 
 def ref_step(p, gr, buf, lr, max_norm, momentum, wd, grad_div):
@@ -54,8 +21,8 @@ def ref_step(p, gr, buf, lr, max_norm, momentum, wd, grad_div):
 
 
 # n not a multiple of 4 (scalar tail), both lr forms; clip active (norm ~ 0.05 sqrt(n) >> 0.1), inactive (max_norm 1e6) and off (<= 0);
-# grad_div 1 / 0.25; weight decay on
-@pytest.mark.parametrize("n", [7, 1030, 262147])
+# grad_div 1 / 0.25; weight decay on.  4194307 > 2048 blocks x 256 lanes x 4 floats: the grid-stride loop runs twice and the scalar tail follows it
+@pytest.mark.parametrize("n", [7, 1030, 262147, 4194307])
 @pytest.mark.parametrize("lr_form", ["table", "two"])
 @pytest.mark.parametrize("max_norm", [0.1, 1e6, 0.0])
 @pytest.mark.parametrize("grad_div", [1.0, 0.25])
@@ -106,22 +73,33 @@ def test_five_steps_vs_torch_sgd():
     assert float(a.state[0]) == 5.0
 
 
-@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
-def test_nonfinite_gradient_skips_the_update(bad):
-    """A NaN / Inf gradient: p and buf bit-unchanged, the step count unchanged, the skip latched in state[3]; the next finite step runs."""
-    n = 1031
+def nonfinite_skip(bad, n, where):
     a = Arenas(n, seed=9, lr0=0.1, lr1=0.01, split=512)
     a.step(0.1, 0.9, 1e-4)                      # one real step first: a live buffer
     p0, b0 = a.p.clone(), a.buf.clone()
-    a.g[n - 2] = bad                            # in the scalar tail: the skip must hold for every block, not just the one that reads it
+    a.g[where] = bad                            # the skip must hold for every block, not just the one that reads it
     a.step(0.1, 0.9, 1e-4)
     assert torch.equal(a.p, p0) and torch.equal(a.buf, b0)
     st = a.state.cpu().tolist()
     assert st[0] == 1.0 and st[3] == 1.0 and not np.isfinite(st[2])
-    a.g[n - 2] = 0.0
+    a.g[where] = 0.0
     a.step(0.1, 0.9, 1e-4)
     st = a.state.cpu().tolist()
     assert st[0] == 2.0 and st[3] == 1.0 and not torch.equal(a.p, p0)
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_nonfinite_gradient_skips_the_update(bad):
+    """A NaN / Inf gradient: p and buf bit-unchanged, the step count unchanged, the skip latched in state[3]; the next finite step runs."""
+    nonfinite_skip(bad, 1031, 1031 - 2)         # in the scalar tail
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_nonfinite_gradient_in_the_last_float4_of_the_grid_stride_case(bad):
+    """The same with more elements than one pass of the grid covers (2048 blocks x 256 lanes x 4 floats): the value sits in the last float4,
+    which the loop's second iteration reads."""
+    n = 4194307
+    nonfinite_skip(bad, n, (n & ~3) - 2)
 
 
 def test_rejects_misaligned_arenas_and_odd_split():
