@@ -56,6 +56,8 @@ def get_args_parser():
     p.add_argument("--scale_factor", default=32, type=int, help="val / test images are resized to a multiple of this (A2/infer.py)")
     p.add_argument("--split", default="val", type=str, help="infer.py: val or test")
     p.add_argument("--cache_mode", default=False, action="store_true")
+    p.add_argument("--ap_on_host", action="store_true",
+                   help="infer.py: box AP through coco_ap's interpreted host path instead of the device matcher (same numbers, minutes on crowded splits)")
     # additions of this build (the reference hard-codes batch 1 on one GPU)
     p.add_argument("--dataset", default="fsc147", choices=["fsc147", "fscd_lvis"], help="reader used without --synthetic")
     p.add_argument("--images_per_gpu", default=2, type=int, help="local batch of the data-parallel trainer")

@@ -20,6 +20,12 @@ accumulate / summarize, bbox path, no crowd regions in FSC-147):
 PARITY UNPINNED: there is no pycocotools here to generate golden vectors from, and the reference holds no AP fixtures.  The tests
 (`tests/test_coco_ap.py`) pin the restatement to hand-derived cases and to the invariants of the definition only.  It is host-side
 post-processing on a json pair -- not part of the step `bench.py` measures.
+
+DEVICE PATH (`device=` a CUDA device on box_iou_xywh / average_precision / summarize / ap_from_json; `device=None`, the default, is the host
+code below, untouched, and stays the checker): `pack_images` flattens all images into packed float64 arrays + offset tables (detections in
+evaluation order), ONE `cdetr_coco_match` launch (csrc/coco_eval.hip) matches every image under every area range and IoU threshold, the
+flags come back in one copy and `accumulate` forms `precision[T, R]` with array operations -- the same float64 operations in the same
+order as the loops of `average_precision`, so the two paths return EQUAL numbers (tests/test_coco_ap_device_cpu.py, _gpu.py).
 """
 import json
 
@@ -37,10 +43,16 @@ def reference_box(b):
     return [int(cx - w / 2), int(cy - h / 2), int(w), int(h)]
 
 
-def box_iou_xywh(dt, gt):
-    """IoU matrix [len(dt), len(gt)] of xywh boxes (pycocotools maskApi bbIou, no crowd)."""
+def box_iou_xywh(dt, gt, device=None):
+    """IoU matrix [len(dt), len(gt)] of xywh boxes (pycocotools maskApi bbIou, no crowd).  `device`: a CUDA device = the same matrix, bit for
+    bit, from cdetr_box_iou_xywh."""
     dt = np.asarray(dt, dtype=np.float64).reshape(-1, 4)
     gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4)
+    if device is not None:
+        import torch
+        from . import ops
+        with torch.cuda.device(_cuda(device)):
+            return ops.box_iou_xywh(torch.from_numpy(dt).to(device), torch.from_numpy(gt).to(device)).cpu().numpy()
     if len(dt) == 0 or len(gt) == 0:
         return np.zeros((len(dt), len(gt)))
     da, ga = dt[:, 2] * dt[:, 3], gt[:, 2] * gt[:, 3]
@@ -89,9 +101,104 @@ def _evaluate_image(dts, gts, area_rng, max_det):
     return np.array([d["score"] for d in dts], dtype=np.float64), dtm >= 0, dt_ig, int((~g_ig).sum())
 
 
-def average_precision(gt_by_img, dt_by_img, area="all", max_det=MAX_DETS):
+def pack_images(gt_by_img, dt_by_img, max_det=MAX_DETS):
+    """The dict form of `average_precision`'s inputs -> packed arrays for `cdetr_coco_match` (host work, no device needed).  Images in
+    sorted-id order, those with neither ground truth nor detection left out (as `average_precision` skips them); image b owns ground truths
+    gt_off[b]:gt_off[b + 1] (original order) and detections dt_off[b]:dt_off[b + 1], the latter in EVALUATION order: descending score,
+    stable (equal scores keep their input order), cut at `max_det` -- the `d_order` of `_evaluate_image`.
+    -> dict: image_ids, gt_boxes f64 [G, 4], gt_area f64 [G], gt_ignore u8 [G] (ignore or iscrowd), gt_off i32 [B + 1], dt_boxes f64 [D, 4],
+    dt_area f64 [D], dt_score f64 [D], dt_off i32 [B + 1], g_max (largest ground-truth count of one image)."""
+    ids = [i for i in sorted(set(gt_by_img) | set(dt_by_img)) if gt_by_img.get(i) or dt_by_img.get(i)]
+    gts = [gt_by_img.get(i, []) for i in ids]
+    dts = []
+    for i in ids:
+        d = dt_by_img.get(i, [])
+        dts.append([d[j] for j in np.argsort([-x["score"] for x in d], kind="mergesort")[:max_det]])
+    flat_g = [g for gl in gts for g in gl]
+    flat_d = [d for dl in dts for d in dl]
+    return {"image_ids": ids,
+            "gt_boxes": np.array([g["bbox"] for g in flat_g], dtype=np.float64).reshape(-1, 4),
+            "gt_area": np.array([g["area"] for g in flat_g], dtype=np.float64),
+            "gt_ignore": np.array([bool(g.get("ignore", 0)) or bool(g.get("iscrowd", 0)) for g in flat_g], dtype=np.uint8),
+            "gt_off": np.concatenate([[0], np.cumsum([len(gl) for gl in gts])]).astype(np.int32),
+            "dt_boxes": np.array([d["bbox"] for d in flat_d], dtype=np.float64).reshape(-1, 4),
+            "dt_area": np.array([d.get("area", d["bbox"][2] * d["bbox"][3]) for d in flat_d], dtype=np.float64),
+            "dt_score": np.array([d["score"] for d in flat_d], dtype=np.float64),
+            "dt_off": np.concatenate([[0], np.cumsum([len(dl) for dl in dts])]).astype(np.int32),
+            "g_max": max([len(gl) for gl in gts], default=0)}
+
+
+def accumulate(scores, matched, ignored, npig):
+    """The tail of `average_precision` as array operations: all images' detections (scores [N], flags [T, N], images concatenated in
+    `pack_images` order) merged by descending score (stable), cumulative tp / fp, precision envelope = running maximum from the right,
+    sampled at the 101 recall thresholds.  Same float64 operations in the same order as the loops there: the result is EQUAL, not close."""
+    T, R = len(IOU_THRS), len(REC_THRS)
+    if npig == 0:
+        return -np.ones((T, R))
+    precision = np.zeros((T, R))
+    order = np.argsort(-np.asarray(scores, dtype=np.float64), kind="mergesort")
+    matched = np.asarray(matched, dtype=bool).reshape(T, -1)[:, order]
+    ignored = np.asarray(ignored, dtype=bool).reshape(T, -1)[:, order]
+    N = matched.shape[1]
+    if N == 0:
+        return precision
+    tps = np.cumsum(matched & ~ignored, axis=1, dtype=np.float64)
+    fps = np.cumsum(~matched & ~ignored, axis=1, dtype=np.float64)
+    rc = tps / npig
+    pr = tps / (fps + tps + np.spacing(1))
+    pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]
+    for t in range(T):                                                     # thresholds, not detections: searchsorted is one-dimensional
+        inds = np.searchsorted(rc[t], REC_THRS, side="left")
+        precision[t] = np.where(inds < N, pr[t][np.minimum(inds, N - 1)], 0.0)
+    return precision
+
+
+def _cuda(device):
+    import torch
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"coco_ap: device={device} -- the device path runs HIP kernels (device=None is the host path)")
+    return device
+
+
+def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None):
+    """One `cdetr_coco_match` launch for every image of `pack` (from `pack_images`) under the area ranges `areas` ->
+    (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int): `_evaluate_image`'s flags, images side by side.
+    `events`: a pair of torch.cuda.Event recorded around the launch."""
+    import torch
+    from . import ops
+    device = _cuda(device)
+    A, T, B, D = len(areas), len(IOU_THRS), len(pack["image_ids"]), len(pack["dt_score"])
+    if B == 0:
+        return np.zeros((A, T, 0), dtype=bool), np.zeros((A, T, 0), dtype=bool), np.zeros((A, 0), dtype=np.int64)
+    thrs = np.minimum(IOU_THRS, 1 - 1e-10)
+    rng = np.array([AREA_RNG[a] for a in areas], dtype=np.float64).reshape(-1)
+    G = len(pack["gt_area"])
+    f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], pack["dt_boxes"].reshape(-1), pack["dt_area"], thrs, rng])
+    i32 = np.concatenate([pack["gt_off"], pack["dt_off"]]).astype(np.int32)
+    with torch.cuda.device(device):
+        f = torch.from_numpy(f64).to(device)
+        i = torch.from_numpy(i32).to(device)
+        ig = torch.from_numpy(pack["gt_ignore"]).to(device)
+        cuts = np.cumsum([0, 4 * G, G, 4 * D, D, T, 2 * A])
+        gt_boxes, gt_area, dt_boxes, dt_area, d_thrs, d_rng = (f[cuts[k]:cuts[k + 1]] for k in range(6))
+        matched, ignored, npig = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]),
+                                                host=True, events=events)
+    return matched, ignored, npig
+
+
+def _device_precisions(gt_by_img, dt_by_img, areas, max_det, device):
+    pack = pack_images(gt_by_img, dt_by_img, max_det)
+    matched, ignored, npig = match_on_device(pack, device, areas)
+    return [accumulate(pack["dt_score"], matched[a], ignored[a], int(npig[a].sum())) for a in range(len(areas))]
+
+
+def average_precision(gt_by_img, dt_by_img, area="all", max_det=MAX_DETS, device=None):
     """`precision[T, R]` (COCOeval.eval["precision"][:, :, k, a, m]) for one category; -1 everywhere when there is no ground truth.
-    gt_by_img / dt_by_img: {image_id: [ {bbox: xywh, area, (iscrowd), (ignore)} ]} / {image_id: [ {bbox: xywh, score} ]}."""
+    gt_by_img / dt_by_img: {image_id: [ {bbox: xywh, area, (iscrowd), (ignore)} ]} / {image_id: [ {bbox: xywh, score} ]}.
+    `device`: a CUDA device = the matching on the device (one launch for all images), the same array."""
+    if device is not None:
+        return _device_precisions(gt_by_img, dt_by_img, (area,), max_det, device)[0]
     rng = AREA_RNG[area]
     scores, matched, ignored, npig = [], [], [], 0
     for img in sorted(set(gt_by_img) | set(dt_by_img)):
@@ -133,17 +240,23 @@ def _mean(p):
     return float(np.mean(p)) if p.size else -1.0
 
 
-def summarize(gt_by_img, dt_by_img, max_det=MAX_DETS):
-    """The six numbers of A2/eval_all.py:331 (x 100, NaN when undefined): AP, AP50, AP75, APs, APm, APl."""
-    p_all = average_precision(gt_by_img, dt_by_img, "all", max_det)
+def summarize(gt_by_img, dt_by_img, max_det=MAX_DETS, device=None):
+    """The six numbers of A2/eval_all.py:331 (x 100, NaN when undefined): AP, AP50, AP75, APs, APm, APl.
+    `device`: a CUDA device = all four area ranges matched in one launch, the same six numbers."""
+    if device is not None:
+        by_area = dict(zip(AREA_RNG, _device_precisions(gt_by_img, dt_by_img, tuple(AREA_RNG), max_det, device)))
+    else:
+        by_area = None
+    p_all = by_area["all"] if by_area else average_precision(gt_by_img, dt_by_img, "all", max_det)
     vals = {"AP": _mean(p_all), "AP50": _mean(p_all[np.isclose(IOU_THRS, 0.5)]), "AP75": _mean(p_all[np.isclose(IOU_THRS, 0.75)])}
     for key, area in (("APs", "small"), ("APm", "medium"), ("APl", "large")):
-        vals[key] = _mean(average_precision(gt_by_img, dt_by_img, area, max_det))
+        vals[key] = _mean(by_area[area] if by_area else average_precision(gt_by_img, dt_by_img, area, max_det))
     return {k: (v * 100 if v >= 0 else float("nan")) for k, v in vals.items()}
 
 
-def ap_from_json(pred_json, gt_json, image_ids=None):
-    """AP of `predictions_<split>.json` (the wire format of infer.py / A2/infer.py:84-116) against `instances_<split>.json`."""
+def ap_from_json(pred_json, gt_json, image_ids=None, device=None):
+    """AP of `predictions_<split>.json` (the wire format of infer.py / A2/infer.py:84-116) against `instances_<split>.json`.
+    `device`: passed to `summarize`."""
     with open(pred_json) as f:
         pred = json.load(f)
     with open(gt_json) as f:
@@ -159,4 +272,4 @@ def ap_from_json(pred_json, gt_json, image_ids=None):
         if a["image_id"] in ids:
             b = reference_box(a["bbox"])
             dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
-    return summarize(gt_by, dt_by)
+    return summarize(gt_by, dt_by, device=device)

@@ -1964,6 +1964,55 @@ def lsap(cost, plan):
     return idx_i, idx_j, status
 
 
+def box_iou_xywh(dt, gt):
+    """cdetr_box_iou_xywh: float64 IoU matrix [D, G] of xywh boxes dt [D, 4], gt [G, 4] (device tensors), equal to
+    coco_ap.box_iou_xywh's numpy result bit for bit."""
+    dt = dt.to(torch.float64).reshape(-1, 4).contiguous()
+    gt = gt.to(torch.float64).reshape(-1, 4).contiguous()
+    D, G = dt.shape[0], gt.shape[0]
+    iou = torch.zeros((D, G), dtype=torch.float64, device=dt.device)
+    if D and G:
+        check(lib().cdetr_box_iou_xywh(ptr(dt), D, ptr(gt), G, ptr(iou), stream_ptr()), "cdetr_box_iou_xywh")
+    return iou
+
+
+def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, iou_thrs, area_rng, g_max, host=False, events=None):
+    """cdetr_coco_match: COCOeval's greedy matcher for B packed images x A area ranges x T IoU thresholds in one launch (device tensors:
+    float64 boxes [*, 4] / areas / thresholds [T] / ranges [A, 2], uint8 ignore flags, int32 offset tables [B + 1]; detections in evaluation
+    order; g_max = the largest ground-truth count of one image, known on the host).  -> matched [A, T, D], det_ignored [A, T, D] (uint8),
+    npig [A, B] (int32): views of ONE byte buffer; host=True returns them as numpy arrays (bool, bool, int32) after a single copy.
+    events: a pair of torch.cuda.Event recorded right before / after the launch (tools/coco_ap_time.py)."""
+    from ._ffi import CocoMatchDesc
+    dev = gt_off.device
+    B, T, A = gt_off.numel() - 1, iou_thrs.numel(), area_rng.numel() // 2
+    G, D = gt_area.numel(), dt_area.numel()
+    for t, dt_ in ((gt_boxes, torch.float64), (gt_area, torch.float64), (dt_boxes, torch.float64), (dt_area, torch.float64), (iou_thrs, torch.float64),
+                   (area_rng, torch.float64), (gt_ignore, torch.uint8), (gt_off, torch.int32), (dt_off, torch.int32)):
+        if t.dtype != dt_ or not t.is_contiguous():
+            raise RuntimeError(f"coco_match: expected a contiguous {dt_} tensor, got {t.dtype}")
+    if gt_boxes.numel() != 4 * G or gt_ignore.numel() != G or dt_boxes.numel() != 4 * D or dt_off.numel() != B + 1:
+        raise RuntimeError("coco_match: packed arrays of inconsistent sizes")
+    n_flag = A * T * D
+    n_pad = (2 * n_flag + 15) // 16 * 16
+    buf = torch.empty(n_pad + 4 * A * B, dtype=torch.uint8, device=dev)
+    d = CocoMatchDesc()
+    d.B, d.A, d.T, d.Gtot, d.Dtot, d.Gmax = B, A, T, G, D, g_max
+    d.gt_boxes, d.gt_area, d.gt_ignore, d.gt_off = ptr(gt_boxes), ptr(gt_area), ptr(gt_ignore), ptr(gt_off)
+    d.dt_boxes, d.dt_area, d.dt_off = ptr(dt_boxes), ptr(dt_area), ptr(dt_off)
+    d.iou_thrs, d.area_rng = ptr(iou_thrs), ptr(area_rng)
+    d.matched, d.det_ignored, d.npig = buf.data_ptr(), buf.data_ptr() + n_flag, buf.data_ptr() + n_pad
+    if events is not None:
+        events[0].record()
+    check(lib().cdetr_coco_match(C.byref(d), stream_ptr()), "cdetr_coco_match")
+    if events is not None:
+        events[1].record()
+    if host:
+        h = buf.cpu().numpy()
+        return (h[:n_flag].reshape(A, T, D).astype(bool), h[n_flag:2 * n_flag].reshape(A, T, D).astype(bool),
+                h[n_pad:].view("int32").reshape(A, B))
+    return buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
+
+
 class CriterionFn(torch.autograd.Function):
     """SetCriterion's six scalars in one launch (cdetr_criterion_fwd); returns (vec, total) with
     vec = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou, loss_variance] and total = sum_k w6[k] vec[k] (the weighted

@@ -465,6 +465,39 @@ int cdetr_bbox_criterion_fwd(const float* pred_wh, int64_t pred_stride, const fl
 int cdetr_bbox_criterion_bwd(const float* g3, float w_wh, float w_giou, const float* g_wh, const float* g_giou, float* d_coord,
                              int32_t M, void* stream);
 
+/* ---- box-AP evaluation (csrc/coco_eval.hip): pycocotools' COCOeval, bbox path, as restated in counting_detr_amd/coco_ap.py -- what the
+ * reference's offline evaluator runs on the host (A2/eval_all.py:285-312, 496-531).  All values FLOAT64, finite; contraction into FMAs is
+ * switched off in this translation unit, so every IoU equals numpy's bit for bit and `iou >= threshold` / equal-IoU ties resolve as on the host.
+ * cdetr_box_iou_xywh: iou [D][G] of dt [D][4] against gt [G][4] (xywh): inter = max(min(x+w) - max(x), 0) * max(min(y+h) - max(y), 0),
+ *   union = (dw*dh + gw*gh) - inter, iou = union > 0 ? inter / union : 0 (maskApi bbIou, no crowd).  D == 0 or G == 0: nothing is launched.
+ * cdetr_coco_match: COCOeval.evaluateImg for B images x A area ranges x T IoU thresholds in ONE launch (one workgroup per image and range, one
+ *   wave per threshold; the image's ground-truth boxes are staged in LDS).  Images are packed: image b owns ground truths gt_off[b] .. gt_off[b+1]
+ *   and detections dt_off[b] .. dt_off[b+1]; the detections are ALREADY in evaluation order (descending score, stable, cut at maxDets).
+ *   Per (image, range [lo, hi], threshold t), detections in order: a ground truth is ignored when gt_ignore is set or its area is < lo or > hi;
+ *   the detection takes the unmatched non-ignored ground truth of highest IoU >= t (the highest index among equal IoUs); only if there is none,
+ *   by the same rule an unmatched ignored one, and is then ignored itself; a matched ground truth is taken for good (no crowd re-matching); an
+ *   unmatched detection whose area is < lo or > hi is ignored.  npig = the number of non-ignored ground truths.  iou_thrs / area_rng are used as
+ *   given (the caller applies min(t, 1 - 1e-10)).  Gmax = the largest ground-truth count of one image (host-known: it sizes the LDS image;
+ *   limit 4096, CDETR_ERR_UNSUPPORTED beyond; an image whose count exceeds Gmax is left untouched); any number of detections; T <= 16.
+ *   Gtot == 0 / Dtot == 0: the ground-truth / detection and output pointers may be NULL.                                                  */
+typedef struct {
+    int32_t B, A, T, Gtot, Dtot, Gmax;
+    const double* gt_boxes;     /* [Gtot][4] xywh */
+    const double* gt_area;      /* [Gtot] */
+    const uint8_t* gt_ignore;   /* [Gtot] ignore or iscrowd */
+    const int32_t* gt_off;      /* [B+1] */
+    const double* dt_boxes;     /* [Dtot][4] xywh */
+    const double* dt_area;      /* [Dtot] */
+    const int32_t* dt_off;      /* [B+1] */
+    const double* iou_thrs;     /* [T] */
+    const double* area_rng;     /* [A][2] */
+    uint8_t* matched;           /* [A][T][Dtot] */
+    uint8_t* det_ignored;       /* [A][T][Dtot] */
+    int32_t* npig;              /* [A][B] */
+} cdetr_coco_match_desc;
+int cdetr_box_iou_xywh(const double* dt, int32_t D, const double* gt, int32_t G, double* iou, void* stream);
+int cdetr_coco_match(const cdetr_coco_match_desc* d, void* stream);
+
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);
 /* Stream plumbing of the trainer (no reference counterpart: the reference runs one stream and drains it every step, A2/engine.py:33-57).

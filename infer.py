@@ -6,7 +6,8 @@ predictions written in the reference's wire format (COCO-style json: bbox = [cx,
 the query's reference point, one `images` entry per image) to <output_dir>/predictions_<split>.json, then MAE / RMSE / NAE /
 SRE of the predicted counts against the ground-truth instance counts, and -- when the split's `instances_<split>.json` is there -- the box AP /
 AP50 / AP75 / APs / APm / APl of A2/eval_all.py:285-331 from a dependency-free restatement of pycocotools' COCOeval
-(counting_detr_amd/coco_ap.py; parity unpinned: there is no pycocotools in this image to check it against).
+(counting_detr_amd/coco_ap.py; parity unpinned: there is no pycocotools in this image to check it against).  On a CUDA device the AP's
+matching runs there (one cdetr_coco_match launch for the split); `--ap_on_host` keeps the interpreted host path, which gives the same numbers.
 
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
 """
@@ -112,7 +113,9 @@ def main(args):
     gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
     if os.path.isfile(gt_json):
         from counting_detr_amd.coco_ap import ap_from_json
-        metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json))
+        # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
+        ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None
+        metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
     print(json.dumps(metrics))
     with open(os.path.join(args.output_dir, "results_" + args.split + ".txt"), "w") as f:
         f.write(json.dumps(metrics) + "\n")

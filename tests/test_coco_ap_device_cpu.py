@@ -1,0 +1,152 @@
+"""Host side of the device box-AP path (counting_detr_amd/coco_ap.py: pack_images, accumulate; the two C-ABI entries of csrc/coco_eval.hip):
+what can be checked without a GPU.  The checker is coco_ap's host path (`_evaluate_image`, `average_precision`), which the device path
+leaves untouched.  tests/test_coco_ap_device_gpu.py compares the kernels themselves."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from counting_detr_amd import coco_ap as ca
+
+import coco_ap_cases as cc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def L():
+    from counting_detr_amd.build import build_lib
+    build_lib(verbose=False)
+    from counting_detr_amd import _ffi
+    return _ffi.lib()
+
+
+def test_entries_exported_and_declared(L):
+    from counting_detr_amd import _ffi
+    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
+    for name in ("cdetr_box_iou_xywh", "cdetr_coco_match"):
+        assert name in _ffi.EXPORTS and hasattr(L, name)
+        assert re.search(r"^int " + name + r"\(", src, flags=re.M), name
+    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_coco_match_desc\s*;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in body.split(";") if decl.strip() for nm in decl.split(",")]
+    assert names == [f[0] for f in _ffi.CocoMatchDesc._fields_]
+    assert "coco_eval.hip" in __import__("counting_detr_amd.build", fromlist=["SOURCES"]).SOURCES
+
+
+def test_bad_arguments_are_refused_before_any_launch(L):
+    from counting_detr_amd import _ffi
+    d = _ffi.CocoMatchDesc()
+    rc = L.cdetr_coco_match(ctypes.byref(d), None)
+    assert rc < 0 and b"cdetr_coco_match" in L.cdetr_last_error()
+    rc = L.cdetr_coco_match(None, None)
+    assert rc < 0 and b"cdetr_coco_match" in L.cdetr_last_error()
+    d.B, d.A, d.T, d.Gtot, d.Dtot, d.Gmax = 1, 4, 10, 5000, 10, 4097          # more ground truths in one image than the matcher holds
+    one = ctypes.c_double(0)
+    for f, _ in _ffi.CocoMatchDesc._fields_[6:]:
+        setattr(d, f, ctypes.addressof(one))                                    # non-null: the capacity check is what refuses
+    rc = L.cdetr_coco_match(ctypes.byref(d), None)
+    assert rc < 0 and b"cdetr_coco_match" in L.cdetr_last_error() and b"4097" in L.cdetr_last_error()
+    d.Gmax, d.T = 100, 17
+    assert L.cdetr_coco_match(ctypes.byref(d), None) < 0 and b"cdetr_coco_match" in L.cdetr_last_error()
+    rc = L.cdetr_box_iou_xywh(None, 3, None, 2, None, None)
+    assert rc < 0 and b"cdetr_box_iou_xywh" in L.cdetr_last_error()
+    rc = L.cdetr_box_iou_xywh(None, -1, None, 2, None, None)
+    assert rc < 0 and b"cdetr_box_iou_xywh" in L.cdetr_last_error()
+
+
+def test_device_path_refuses_a_cpu_device():
+    g, d = {1: [cc.gt([0, 0, 10, 10])]}, {1: [cc.dt([0, 0, 10, 10], 0.9)]}
+    with pytest.raises(RuntimeError, match="host path"):
+        ca.summarize(g, d, device="cpu")
+    with pytest.raises(RuntimeError, match="host path"):
+        ca.box_iou_xywh([[0, 0, 1, 1]], [[0, 0, 1, 1]], device="cpu")
+
+
+def test_pack_images_order_cut_offsets_and_empty_images():
+    gts = {5: [cc.gt([0, 0, 10, 10]), cc.gt([1, 2, 3.5, 4], iscrowd=1), cc.gt([7, 7, 2, 2], ignore=1)],
+           2: [],                                                              # detections only
+           9: [cc.gt([5, 5, 5, 5])],                                           # ground truth only
+           4: []}                                                              # neither: left out, as average_precision skips it
+    dts = {5: [cc.dt([0, 0, 1, 1], 0.5), cc.dt([0, 0, 2, 2], 0.9), cc.dt([0, 0, 3, 3], 0.5), cc.dt([0, 0, 4, 4], 0.9), cc.dt([0, 0, 5, 5], 0.1)],
+           2: [{"bbox": [1.0, 1.0, 2.0, 3.0], "score": 0.3}],                  # no "area": w * h
+           4: []}
+    p = ca.pack_images(gts, dts)
+    assert p["image_ids"] == [2, 5, 9]
+    assert p["gt_off"].dtype == np.int32 and p["gt_off"].tolist() == [0, 0, 3, 4] and p["dt_off"].tolist() == [0, 1, 6, 6]
+    assert p["g_max"] == 3
+    # repeated scores keep their input order (stable descending sort): 0.9 (w 2), 0.9 (w 4), 0.5 (w 1), 0.5 (w 3), 0.1
+    assert p["dt_boxes"][1:, 2].tolist() == [2.0, 4.0, 1.0, 3.0, 5.0] and p["dt_score"].tolist() == [0.3, 0.9, 0.9, 0.5, 0.5, 0.1]
+    assert p["dt_area"].tolist() == [6.0, 4.0, 16.0, 1.0, 9.0, 25.0]
+    assert p["gt_ignore"].dtype == np.uint8 and p["gt_ignore"].tolist() == [0, 1, 1, 0]
+    assert p["gt_boxes"].shape == (4, 4) and p["gt_boxes"][1].tolist() == [1.0, 2.0, 3.5, 4.0] and p["gt_area"].tolist() == [100.0, 14.0, 4.0, 25.0]
+    for k in ("gt_boxes", "gt_area", "dt_boxes", "dt_area", "dt_score"):
+        assert p[k].dtype == np.float64
+    # the cut at max_det is made AFTER the sort
+    p2 = ca.pack_images(gts, dts, max_det=3)
+    assert p2["dt_off"].tolist() == [0, 1, 4, 4] and p2["dt_boxes"][1:, 2].tolist() == [2.0, 4.0, 1.0]
+    # the order equals _evaluate_image's own, image by image
+    g, d = cc.tie_family(seed=3, shapes=((20, 60), (0, 7), (9, 0)))
+    p3 = ca.pack_images(g, d, max_det=50)
+    for b, img in enumerate(p3["image_ids"]):
+        s, _, _, _ = ca._evaluate_image(d[img], g[img], ca.AREA_RNG["all"], 50)
+        assert np.array_equal(p3["dt_score"][p3["dt_off"][b]:p3["dt_off"][b + 1]], s)
+    e = ca.pack_images({}, {})
+    assert e["image_ids"] == [] and e["gt_off"].tolist() == [0] and e["gt_boxes"].shape == (0, 4) and e["g_max"] == 0
+
+
+def _tail_equals_loops(gts, dts, area, max_det=ca.MAX_DETS):
+    want = ca.average_precision(gts, dts, area, max_det)
+    s, m, ig, n = cc.host_flags(gts, dts, area, max_det)
+    assert np.array_equal(s, ca.pack_images(gts, dts, max_det)["dt_score"])
+    got = ca.accumulate(s, m, ig, int(n.sum()))
+    assert got.dtype == want.dtype and np.array_equal(got, want), (area, np.abs(got - want).max())
+    return want
+
+
+def test_vectorised_tail_equals_average_precision():
+    g, d = cc.tie_family()
+    for area in ca.AREA_RNG:
+        p = _tail_equals_loops(g, d, area)
+        assert (p >= 0).all()
+    g, d = cc.float_family()
+    for area in ca.AREA_RNG:
+        _tail_equals_loops(g, d, area)
+    _tail_equals_loops(g, d, "all", max_det=17)
+
+
+def test_vectorised_tail_on_the_edges():
+    # an all-ignored range: every ground truth is small, "large" has npig == 0 -> all -1
+    g = {1: [cc.gt([0, 0, 10, 10]), cc.gt([30, 30, 12, 12])], 2: [cc.gt([5, 5, 8, 8])]}
+    d = {1: [cc.dt([0, 0, 10, 10], 0.9), cc.dt([100, 100, 200, 200], 0.8)], 2: [cc.dt([5, 5, 8, 9], 0.7)]}
+    p = _tail_equals_loops(g, d, "large")
+    assert (p == -1).all()
+    # recall stops short of 1: [30, 30, 12, 12] is never found -> zeros past recall 2/3
+    p = _tail_equals_loops(g, d, "all")
+    assert p[0, 66] > 0 and p[0, 67] == 0.0
+    # ground truth without any detection, detections without ground truth, nothing at all
+    assert (_tail_equals_loops(g, {}, "all") == 0).all()
+    assert (_tail_equals_loops({}, d, "all") == -1).all()
+    assert (_tail_equals_loops({}, {}, "all") == -1).all()
+    # the hand-derived case of tests/test_coco_ap.py
+    s = 50 * 0.38 / 1.62
+    g = {7: [cc.gt([10, 10, 40, 40]), cc.gt([100, 100, 50, 50])]}
+    d = {7: [cc.dt([10, 10, 40, 40], 0.9), cc.dt([300, 300, 30, 30], 0.8), cc.dt([100 + s, 100, 50, 50], 0.7)]}
+    p = _tail_equals_loops(g, d, "all")
+    assert p[0, 50] == pytest.approx(1.0) and p[0, 51] == pytest.approx(2 / 3) and p[9, 51] == 0.0
+
+
+def test_tie_family_exercises_what_it_is_meant_to():
+    """The bars of the GPU test, on the host path alone: ties between ground truths, IoUs exactly on a threshold, repeated scores, both
+    kinds of ignored detections in every bounded area range, matches that depend on the threshold."""
+    st = cc.tie_statistics(*cc.tie_family())
+    cc.assert_tie_bars(st)
+    assert st["small"]["matches_first"] != st["medium"]["matches_first"] or st["all"]["matches_first"] != st["medium"]["matches_first"]
+
+
+def test_infer_cli_has_the_host_switch():
+    from counting_detr_amd.args import get_args_parser
+    assert get_args_parser().parse_args([]).ap_on_host is False
+    assert get_args_parser().parse_args(["--ap_on_host"]).ap_on_host is True
