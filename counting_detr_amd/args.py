@@ -90,6 +90,9 @@ def get_args_parser():
     p.add_argument("--exemplar_mode", default="per_image", choices=["per_image", "reference"],
                    help="per_image: image b is conditioned on its own exemplars; reference: rects[0] for the whole batch "
                         "(A2/models/backbone.py:122 -- exact only at batch 1)")
+    p.add_argument("--device_preprocess", action="store_true",
+                   help="the DataLoader workers only decode; resize (PIL-exact), normalisation and padding run on the device in one launch per "
+                        "batch (cdetr_image_prep) -- the same image / mask tensors bit for bit")
     return p
 
 
@@ -146,6 +149,9 @@ def get_args_parser_stage1():
     p.add_argument("--no_graph_cache", dest="graph_cache", action="store_false",
                    help="train with the stream-ordered step instead of cached HIP graphs (one per padded image size / points shape)")
     p.add_argument("--graph_cache_size", default=32, type=int)
+    p.add_argument("--device_preprocess", action="store_true",
+                   help="the DataLoader workers only decode; resize (PIL-exact), normalisation and padding run on the device in one launch per "
+                        "batch (cdetr_image_prep) -- the same image / mask tensors bit for bit")
     return p
 
 

@@ -2013,6 +2013,33 @@ def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, 
     return buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
 
 
+def image_prep(raw, events=None):
+    """cdetr_image_prep: the `raw` part of a batch from data.collate_raw / collate_stage1_raw, already on the device (uint8 `pixels`, int32
+    `images` records and `tables`, fp32 `lut` [3, 256]; ints Hm, Wm, max_taps, max_rows) -> (image fp32 [B, 3, Hm, Wm], mask bool [B, Hm, Wm]),
+    torch.equal to what data.collate builds from the host-resized samples.  One launch on the current stream; it writes every element of
+    both outputs.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/image_prep_time.py)."""
+    from ._ffi import ImagePrepDesc
+    pixels, images, tables, lut = raw["pixels"], raw["images"], raw["tables"], raw["lut"]
+    for name, t, dt_ in (("pixels", pixels, torch.uint8), ("images", images, torch.int32), ("tables", tables, torch.int32), ("lut", lut, torch.float32)):
+        if t.dtype != dt_ or not t.is_contiguous():
+            raise RuntimeError(f"image_prep: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    if images.dim() != 2 or images.shape[1] != 12 or lut.numel() != 768:
+        raise RuntimeError(f"image_prep: `images` must be [B, 12] and `lut` [3, 256], got {tuple(images.shape)} and {tuple(lut.shape)}")
+    B, Hm, Wm = images.shape[0], int(raw["Hm"]), int(raw["Wm"])
+    image = torch.empty((B, 3, Hm, Wm), dtype=torch.float32, device=pixels.device)
+    mask = torch.empty((B, Hm, Wm), dtype=torch.bool, device=pixels.device)
+    d = ImagePrepDesc()
+    d.B, d.Hm, d.Wm, d.max_taps, d.max_rows = B, Hm, Wm, int(raw["max_taps"]), int(raw["max_rows"])
+    d.pixels, d.pixel_bytes, d.images, d.tables, d.table_ints = ptr(pixels), pixels.numel(), ptr(images), ptr(tables), tables.numel()
+    d.lut, d.image, d.mask = ptr(lut), ptr(image), ptr(mask)
+    if events is not None:
+        events[0].record()
+    check(lib().cdetr_image_prep(C.byref(d), stream_ptr()), "cdetr_image_prep")
+    if events is not None:
+        events[1].record()
+    return image, mask
+
+
 class CriterionFn(torch.autograd.Function):
     """SetCriterion's six scalars in one launch (cdetr_criterion_fwd); returns (vec, total) with
     vec = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou, loss_variance] and total = sum_k w6[k] vec[k] (the weighted

@@ -498,6 +498,45 @@ typedef struct {
 int cdetr_box_iou_xywh(const double* dt, int32_t D, const double* gt, int32_t G, double* iou, void* stream);
 int cdetr_coco_match(const cdetr_coco_match_desc* d, void* stream);
 
+/* ---- image batches prepared on the device (csrc/image_prep.hip): what the reference's readers do per image on the host -- PIL resize,
+ * ToTensor + Normalize (A2/data/fsc147.py:22-24, 75-77) -- plus this build's zero-padding to the batch maximum and its padding mask
+ * (counting_detr_amd/data.py collate), in ONE launch, BIT-EQUAL to that host path.
+ * cdetr_image_prep: image [B][3][Hm][Wm] fp32 and mask [B][Hm][Wm] bytes (1 = padding) from the un-resized uint8 RGB pixels of the batch.
+ *   pixels : every image's [in_h][in_w][3] bytes, packed; images: one record of CDETR_IMAGE_PREP_RECORD_INTS int32 per image =
+ *            { byte offset into pixels, in_h, in_w, out_h, out_w, h_bounds, h_coeffs, h_taps, v_bounds, v_coeffs, v_taps, 0 },
+ *            the four table fields being offsets into `tables` in int32 entries.
+ *   tables : per axis, bounds [out][2] = (first source sample, number of taps) and coeffs [out][taps] = Pillow's 8-bit coefficients
+ *            (22 fractional bits; data.resample_tables).  Each pass: clamp((2^21 + sum sample * coeff) >> 22, 0, 255), horizontal first
+ *            into uint8, vertical over that (Pillow's ImagingResample order); an unchanged axis carries the identity table (1 tap of 2^22).
+ *   lut    : [3][256] fp32, the normalised value of byte v in channel c, built on the host with the host path's own expressions.
+ *   Output pixel (y, x) of image b: inside out_h x out_w the resampled, normalised value and mask 0, elsewhere 0.0f and mask 1.  EVERY
+ *   element of image and mask is written (no fill needed beforehand).  image must be 16-byte, mask 4-byte aligned.
+ *   Supported scales, set by the LDS tile (CDETR_IMAGE_PREP_TILE_H x _TILE_W output pixels per workgroup): at most _MAX_TAPS taps per
+ *   output sample and _MAX_ROWS source rows under _TILE_H output rows, i.e. DOWNSCALES up to 4x per axis for bicubic and bilinear
+ *   (17 taps, 141 rows) and upscales of any factor.  max_taps / max_rows are the batch's own maxima, known on the host:
+ *   CDETR_ERR_UNSUPPORTED beyond the limits (data.collate_raw resizes such an image on the host and passes it with identity tables).
+ *   Records and table entries are range-checked on the device against pixel_bytes / table_ints before they address anything: an
+ *   inconsistent record gives an all-padding image, never an access outside the buffers.                                          */
+#define CDETR_IMAGE_PREP_TILE_H 32
+#define CDETR_IMAGE_PREP_TILE_W 64
+#define CDETR_IMAGE_PREP_MAX_TAPS 20
+#define CDETR_IMAGE_PREP_MAX_ROWS 160
+#define CDETR_IMAGE_PREP_RECORD_INTS 12
+typedef struct {
+    int32_t B, Hm, Wm;
+    int32_t max_taps, max_rows;  /* largest h_taps / v_taps of the batch; largest source-row span of _TILE_H consecutive output rows */
+    int32_t pad_;
+    const uint8_t* pixels;
+    int64_t pixel_bytes;
+    const int32_t* images;       /* [B][CDETR_IMAGE_PREP_RECORD_INTS] */
+    const int32_t* tables;
+    int64_t table_ints;
+    const float* lut;            /* [3][256] */
+    float* image;                /* [B][3][Hm][Wm] */
+    uint8_t* mask;               /* [B][Hm][Wm] */
+} cdetr_image_prep_desc;
+int cdetr_image_prep(const cdetr_image_prep_desc* d, void* stream);
+
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);
 /* Stream plumbing of the trainer (no reference counterpart: the reference runs one stream and drains it every step, A2/engine.py:33-57).

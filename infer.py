@@ -106,8 +106,11 @@ def main(args):
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(ckpt["model"], strict=True)
     from torch.utils.data import DataLoader
-    ds = data.build_test_dataset(args, image_set=args.split)
-    dl = DataLoader(ds, batch_size=1, shuffle=False, collate_fn=data.collate, num_workers=args.num_workers)
+    raw = bool(getattr(args, "device_preprocess", False))               # workers decode only; resize + normalise + pad on the device
+    ds = data.build_test_dataset(args, image_set=args.split, raw=raw)
+    dl = DataLoader(ds, batch_size=1, shuffle=False, collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers)
+    if raw:
+        dl = data.Prefetcher(dl, device)
     os.makedirs(args.output_dir, exist_ok=True)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split)
     gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")

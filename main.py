@@ -6,7 +6,8 @@ weights only, keys filtered like A2/main.py:195-209) -> per epoch train_one_epoc
 Differences: any number of images per GPU (--images_per_gpu), data-parallel over the GPUs of a node under torchrun
 (RCCL), and --synthetic (seeded tensors; FSC-147 is not available in this environment -- with a dataset, pass a
 DataLoader yielding the reference's sample dicts to `train_one_epoch`).  Without --synthetic the FSC-147 reader of
-counting_detr_amd/data.py feeds the step (batched collate + pinned-memory prefetch).
+counting_detr_amd/data.py feeds the step (batched collate + pinned-memory prefetch); with --device_preprocess the workers only decode
+and the resize / normalisation / padding of a batch is one launch on the prefetch stream (same tensors bit for bit).
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --synthetic --no_aux_loss ...
@@ -92,10 +93,11 @@ def main(args):
     else:                                                               # A2/main.py:146-147 (+ batching, sharding, prefetch)
         from torch.utils.data import DataLoader, DistributedSampler
         from counting_detr_amd import data
-        ds = data.build_dataset(args)
+        raw = bool(getattr(args, "device_preprocess", False))            # workers decode only; the Prefetcher launches cdetr_image_prep
+        ds = data.build_dataset(args, raw=raw)
         sampler = DistributedSampler(ds, shuffle=True, seed=args.seed) if getattr(args, "distributed", False) else None
-        dl = DataLoader(ds, batch_size=args.images_per_gpu, shuffle=(sampler is None), sampler=sampler, collate_fn=data.collate,
-                        num_workers=args.num_workers, drop_last=True, pin_memory=False)
+        dl = DataLoader(ds, batch_size=args.images_per_gpu, shuffle=(sampler is None), sampler=sampler,
+                        collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers, drop_last=True, pin_memory=False)
         loader = data.Prefetcher(dl, device)
     print("Start training")
     start = time.time()
@@ -122,8 +124,11 @@ def main(args):
             import infer as _infer
             from torch.utils.data import DataLoader
             from counting_detr_amd import data
-            dl = DataLoader(data.build_test_dataset(args, image_set=args.split), batch_size=1, shuffle=False, collate_fn=data.collate,
-                            num_workers=args.num_workers)
+            raw = bool(getattr(args, "device_preprocess", False))
+            dl = DataLoader(data.build_test_dataset(args, image_set=args.split, raw=raw), batch_size=1, shuffle=False,
+                            collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers)
+            if raw:
+                dl = data.Prefetcher(dl, device)
             metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split)
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard

@@ -53,12 +53,16 @@ def to_device(loader, device):
         yield {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in b.items()}
 
 
-def loader_for(args, split, points=False, shuffle=False):
+def loader_for(args, split, points=False, shuffle=False, device=None):
+    """The split's DataLoader (host tensors).  --device_preprocess: its workers only decode and a data.Prefetcher on `device` yields device
+    batches whose image / mask come from one cdetr_image_prep launch -- the same tensors bit for bit."""
     from torch.utils.data import DataLoader
     from counting_detr_amd import data
-    ds = data.build_points_dataset(args, split) if points else data.build_dataset_stage1(args, split)
-    return DataLoader(ds, batch_size=1 if points else args.batch_size, shuffle=shuffle, collate_fn=data.collate_stage1,
-                      num_workers=args.num_workers, drop_last=shuffle)
+    raw = bool(getattr(args, "device_preprocess", False))
+    ds = data.build_points_dataset(args, split, raw=raw) if points else data.build_dataset_stage1(args, split, raw=raw)
+    dl = DataLoader(ds, batch_size=1 if points else args.batch_size, shuffle=shuffle,
+                    collate_fn=data.collate_stage1_raw if raw else data.collate_stage1, num_workers=args.num_workers, drop_last=shuffle)
+    return data.Prefetcher(dl, device) if raw else dl
 
 
 @torch.no_grad()
@@ -103,7 +107,7 @@ def main(args):
         if unexpected:
             print("Unexpected Keys: {}".format(unexpected))
         for split in ("train", "val", "test"):
-            ann = stage1.write_pseudo_labels(model, loader_for(args, split, points=True), split, args.output_dir, device=device)
+            ann = stage1.write_pseudo_labels(model, loader_for(args, split, points=True, device=device), split, args.output_dir, device=device)
             print(f"pseudo_bbox_{split}.json: {len(ann['images'])} images, {len(ann['annotations'])} boxes")
         return
 
@@ -112,7 +116,7 @@ def main(args):
         checkpoint, _, _ = ckpt_io.resume_model(model, args.resume)
 
     if args.eval:
-        stats = evaluate(model, criterion, loader_for(args, "val"), device)
+        stats = evaluate(model, criterion, loader_for(args, "val", device=device), device)
         print("validation:", json.dumps(stats))
         return
 
@@ -131,7 +135,7 @@ def main(args):
         if args.synthetic:
             loader = SyntheticLoader(args, device, args.steps_per_epoch, size=tuple(args.synthetic_size))
         else:
-            loader = to_device(loader_for(args, "train", shuffle=True), device)
+            loader = to_device(loader_for(args, "train", shuffle=True, device=device), device)
         stats = train_one_epoch(trainer, loader, epoch, print_freq=args.print_freq)
         trainer.lr_scheduler_step()
         paths = [output_dir / "checkpoint.pth"]
