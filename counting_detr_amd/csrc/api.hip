@@ -26,8 +26,9 @@ namespace {
 struct TuneEnvCheck {
     TuneEnvCheck() {
         if (getenv("CDETR_TUNING") != nullptr || environ == nullptr) return;
-        static const char* const knobs[] = {"CDETR_GEMM_FEWROW_SPLIT", "CDETR_GEMM_SPLITK", "CDETR_GEMM_VARIANT", "CDETR_LSAP_GENERIC",
-                                            "CDETR_RCDA_HS", "CDETR_RCDA_NW", "CDETR_RCDA_NW5", "CDETR_WGRAD_VARIANT"};
+        static const char* const knobs[] = {"CDETR_DIRECT_MAX_BLOCKS", "CDETR_GEMM_DL", "CDETR_GEMM_FEWROW_SPLIT", "CDETR_GEMM_SPLITK", "CDETR_GEMM_VARIANT",
+                                            "CDETR_LN_BWD_ROWS", "CDETR_LSAP_GENERIC", "CDETR_RCDA_HS", "CDETR_RCDA_PROBE", "CDETR_WGRAD_KP",
+                                            "CDETR_WGRAD_VARIANT"};
         for (const char* k : knobs)
             if (getenv(k) != nullptr)
                 fprintf(stderr, "libcdetr_hip: %s is set but CDETR_TUNING is not -- per-call tuning knobs are ignored without it\n", k);

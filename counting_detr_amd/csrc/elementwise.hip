@@ -1195,6 +1195,15 @@ extern "C" int cdetr_groupnorm_bwd_ws(const float* dy, const float* x, const flo
     return cdetr_launch_status("cdetr_groupnorm_bwd_ws");
 }
 
+// workgroups of ln_bwd_kernel before the cap: 4 rows each (one per wave) up to 2048 rows, CDETR_LN_BWD_ROWS (A/B knob, read under CDETR_TUNING;
+// default 32) rows each on long inputs
+static int ln_bwd_blocks(int rows) {
+    if (rows <= 2048) return (rows + 3) / 4;
+    const char* e = cdetr_tune_env("CDETR_LN_BWD_ROWS");
+    const int rpb = e ? atoi(e) : 32;
+    return (rows + rpb - 1) / rpb;
+}
+
 extern "C" int cdetr_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                                    const float* add, float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t C, void* dx16, void* stream) {
     CDETR_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && rows >= 0, "cdetr_layernorm_bwd: null pointer");
@@ -1203,8 +1212,7 @@ extern "C" int cdetr_layernorm_bwd(const float* dy, const float* x, const float*
     if (rows == 0) return CDETR_OK;
     // >= 4 rows per wave amortise the per-workgroup dgamma / dbeta atomics on long inputs; short ones (decoder: 600 rows) are latency
     // bound, one row per wave there
-    static const int rpb = getenv("CDETR_LN_BWD_ROWS") ? atoi(getenv("CDETR_LN_BWD_ROWS")) : 32;      // rows per workgroup on long inputs (A/B)
-    int blocks = rows <= 2048 ? (rows + 3) / 4 : (rows + rpb - 1) / rpb;
+    int blocks = ln_bwd_blocks(rows);
     if (blocks > 512) blocks = 512;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, x, mean, rstd, gamma,
@@ -1220,8 +1228,7 @@ extern "C" int cdetr_layernorm_bwd_merge(const float* dy, const float* g1, const
     CDETR_CHECK_ARG(!Br == !Bc && (!Br || (H > 0 && W > 0 && rows % (H * W) == 0)), "cdetr_layernorm_bwd_merge: Br / Bc come as a pair, rows = N * H * W");
     CDETR_CHECK_ARG(C == 256, "cdetr_layernorm_bwd_merge: C must be 256 (got %d)", C);
     if (rows == 0) return CDETR_OK;
-    static const int rpb = getenv("CDETR_LN_BWD_ROWS") ? atoi(getenv("CDETR_LN_BWD_ROWS")) : 32;
-    int blocks = rows <= 2048 ? (rows + 3) / 4 : (rows + rpb - 1) / rpb;
+    int blocks = ln_bwd_blocks(rows);
     if (blocks > 512) blocks = 512;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, x, mean, rstd, gamma,
                        add, dx, dgamma, dbeta, rows, C, g1, g2, acc1, acc2, Br, Bc, sr, sc, Br ? H : 1, Br ? W : 1, reinterpret_cast<__bf16*>(dx16));

@@ -1942,8 +1942,7 @@ int raise_lds(F func, int bytes, const char* what) {
 
 // bf16 twin of A usable: given, 8-element granularity of every row / batch stride (16-byte loads of 8 k-values)
 inline bool gemm_has_a_twin(const cdetr_gemm_desc& d) {
-    static const int on = getenv("CDETR_GEMM_A16") ? atoi(getenv("CDETR_GEMM_A16")) : 1;
-    return on && d.A16 && (d.lda & 7) == 0 && (d.sA & 7) == 0 && (d.sA2 & 7) == 0 && (reinterpret_cast<uintptr_t>(d.A16) & 15) == 0;
+    return d.A16 && (d.lda & 7) == 0 && (d.sA & 7) == 0 && (d.sA2 & 7) == 0 && (reinterpret_cast<uintptr_t>(d.A16) & 15) == 0;
 }
 
 // Slices per output tile (1 = no split).  The tile kernels hide their load latency with OTHER workgroups of the same CU; a problem of two
@@ -2037,7 +2036,8 @@ int gemm_vec_b(const cdetr_gemm_desc& d) {
 }
 // the kernel classes of the default dispatch (shared by cdetr_gemm and cdetr_gemm_group)
 bool gemm_is_direct(const cdetr_gemm_desc& d, int vecA, int vecB) {
-    static const long direct_max = getenv("CDETR_DIRECT_MAX_BLOCKS") ? atol(getenv("CDETR_DIRECT_MAX_BLOCKS")) : 48;      // A/B knob
+    const char* e = cdetr_tune_env("CDETR_DIRECT_MAX_BLOCKS");      // A/B knob
+    const long direct_max = e ? atol(e) : 48;
     return d.g.mode == CDETR_ROWS_DENSE && (gemm_blocks(d, 64, 64) <= direct_max || !(vecA && vecB && (d.K % 32) == 0)) && gemm_blocks(d, 64, 64) < 192;
 }
 bool gemm_is_fewrow_split(const cdetr_gemm_desc& d, int vecA, int vecB) {
@@ -2095,9 +2095,11 @@ namespace {
 //     (64 B of hi + 64 B of lo per row and k-tile) are half lines -- the direct-to-LDS kernel wins where the epilogue dominates
 //     (K <= 256: 1.1-1.2x) and loses on the long reductions (3x3, K >= 1024: 0.8-0.95x), -7 % over the sweep AFTER charging every
 //     producer for the lo plane: not the default (the producers only write lo planes under ops.SPLIT_FWD).
-// CDETR_GEMM_DL (read once): 0 = never, 1 = this rule (default), 100 + 10 * tile + stages = force one configuration wherever legal.
+// CDETR_GEMM_DL (tools/dl_sweep.py, read under CDETR_TUNING): 0 = never, 1 = this rule (default), 100 + 10 * tile + stages = force one
+// configuration wherever legal.
 int gemm_dl_choice(const cdetr_gemm_desc& d, int& stages) {
-    static const int mode = getenv("CDETR_GEMM_DL") ? atoi(getenv("CDETR_GEMM_DL")) : 1;
+    const char* dl = cdetr_tune_env("CDETR_GEMM_DL");
+    const int mode = dl ? atoi(dl) : 1;
     if (mode == 0 || !cdetr_gemm_dl_eligible(d)) return -1;
     if (mode >= 100) {
         stages = mode % 10;
@@ -2105,26 +2107,13 @@ int gemm_dl_choice(const cdetr_gemm_desc& d, int& stages) {
     }
     auto blocks = [&](int bm, int bn) { return (long)((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn); };
     stages = 3;
-    // split reduction (stages code 200 + 10 * slices + ring depth, igemm_dl.hip) -- CDETR_DL_SPLITK: 0 = never (default), 1 = this rule.
-    // In the step the rule is neutral (three same-lease pairs, profiles/r5_dl_splitk.txt: the backbone's backward is throughput-bound on
-    // two queues -- a shorter data-gradient launch gives its CUs to the weight gradients beside it, not to the chain): off.
-    // Cold-operand sweep of the data gradients (profiles/r5_dl_splitk.txt): three slices on 64x128 tiles win on the 3x3 convolutions of
-    // 50x50 maps (36-72 k-tiles per tile; 256 -> 256: 22.9 -> 19.5 us, 512 -> 512: 58.0 -> 45.5 us), the exchange (write-through partials,
-    // arrival count, late epilogue operands: ~6 us of round trips) costs more than it hides on every 1x1 shape (K <= 2048: 8-32 k-tiles)
-    auto split_3x3 = [&]() {
-        static const int sm = getenv("CDETR_DL_SPLITK") ? atoi(getenv("CDETR_DL_SPLITK")) : 0;
-        const long wgs = blocks(64, 128);
-        const int nkt_all = (int)((long)d.K / (d.precision == 1 ? 32 : 64) * d.taps);
-        return sm == 1 && d.taps == 9 && d.N % 128 == 0 && d.splitk_ws && wgs <= 384 && nkt_all >= 24 &&
-               (long)SPLITK_COUNTERS * 4 + wgs * 3 * 64 * 128 * 4 <= d.splitk_ws_bytes;
-    };
+    // (Round 5, measured and left off: a split reduction -- three slices on 64x128 tiles -- for the 3x3 data gradients of 50x50 maps.  Cold-operand
+    // sweep, profiles/r5_dl_splitk.txt: 256 -> 256: 22.9 -> 19.5 us, 512 -> 512: 58.0 -> 45.5 us, the exchange costing more than it hides on every
+    // 1x1 shape; in the step the rule was neutral in three same-lease pairs -- the backbone's backward is throughput-bound on two queues, a shorter
+    // data-gradient launch gives its CUs to the weight gradients beside it, not to the chain.)
     if (!d.C) return blocks(64, 64) >= 512 && (long)d.K * d.taps >= 2048 && d.N % 128 == 0 ? 0 : 3;   // no fp32 output: only this kernel can run it
     if (blocks(64, 64) < 192) return -1;                                      // few tiles: the split-reduction forms of the register-staged kernels
     if (d.precision == 3) {
-        if (split_3x3()) {
-            stages = 233;
-            return 2;
-        }
         return ((long)d.K * d.taps >= 2048 && d.N % 128 == 0 && blocks(128, 128) >= 128) ? 0 : 3;
     }
     // split-bf16 x3 with planes given: where the sweep has it ahead -- the expanding 1x1 convolutions (K = planes <= 512, N = 4 K), whose
@@ -2239,7 +2228,8 @@ extern "C" int cdetr_gemm(const cdetr_gemm_desc* dp, void* stream) {
 extern "C" int cdetr_gemm_group(const cdetr_gemm_desc* descs, int32_t n, void* stream) {
     CDETR_CHECK_ARG(n >= 0 && (descs != nullptr || n == 0), "cdetr_gemm_group: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const bool grouping = !(getenv("CDETR_GEMM_GROUP") && atoi(getenv("CDETR_GEMM_GROUP")) == 0) && !getenv("CDETR_GEMM_VARIANT");
+    const char* force_s = cdetr_tune_env("CDETR_GEMM_VARIANT");
+    const bool grouping = !(force_s && atoi(force_s) != 0);      // a forced tile: every problem through cdetr_gemm
     std::vector<int> cls[5];          // direct UB 4 / 8 / 16 (k-contiguous weight), fast 64x128 with a pre-split weight (bf16x3 | plain bf16)
     for (int i = 0; i < n; ++i) {
         const cdetr_gemm_desc& d = descs[i];
@@ -2259,9 +2249,8 @@ extern "C" int cdetr_gemm_group(const cdetr_gemm_desc* descs, int32_t n, void* s
         else if (int rc1 = cdetr_gemm(&d, stream)) return rc1;
     }
     // one launch for a few-row (K <= 256) class next to ONE tile class, when everything fits a single argument table
-    static const int mixed = getenv("CDETR_GEMM_MIXED") ? atoi(getenv("CDETR_GEMM_MIXED")) : 1;
     const int tc = !cls[3].empty() ? 3 : 4;
-    if (mixed && !cls[0].empty() && (cls[3].empty() != cls[4].empty()) && cls[0].size() + cls[tc].size() <= (size_t)GG_MAX) {
+    if (!cls[0].empty() && (cls[3].empty() != cls[4].empty()) && cls[0].size() + cls[tc].size() <= (size_t)GG_MAX) {
         GemmGroupArgs g;
         int m = 0;
         g.blk0[0] = 0;
@@ -2362,22 +2351,19 @@ void direct_wgrad_plan(const cdetr_wgrad_desc& d, int& tilesI, int& tilesJ, int&
 }
 // few-pixel problems (positional MLPs: P = B*(h+w) rows) take the one-wave-per-16x16-tile kernel; from 256 pixels on (the decoder's B*Q = 600
 // rows) the transpose-read tile kernel is faster -- measured on the step: boundary 1024 / 512 / 256 / 64 pixels -> 11.71 / 11.63 / 11.60 /
-// 11.60 ms (CDETR_WGRAD_DIRECT_MAXP moves it for A/B runs)
+// 11.60 ms
 bool wgrad_is_direct(const cdetr_wgrad_desc& d) {
-    static const int maxp = getenv("CDETR_WGRAD_DIRECT_MAXP") ? atoi(getenv("CDETR_WGRAD_DIRECT_MAXP")) : 256;
-    return d.g.mode == CDETR_ROWS_DENSE && (d.P <= maxp || !((d.ldy & 3) == 0 && (d.ldx & 3) == 0 && (d.Nout & 3) == 0 && (d.Cin & 3) == 0)) && d.P <= 1024;
+    return d.g.mode == CDETR_ROWS_DENSE && (d.P <= 256 || !((d.ldy & 3) == 0 && (d.ldx & 3) == 0 && (d.Nout & 3) == 0 && (d.Cin & 3) == 0)) && d.P <= 1024;
 }
 // bf16 twins usable (wgrad_tr16_kernel): plain-bf16 products requested, both twins given, 8-element granularity everywhere
 bool wgrad_has_twins(const cdetr_wgrad_desc& d) {
-    static const int on = getenv("CDETR_WGRAD_TWINS") ? atoi(getenv("CDETR_WGRAD_TWINS")) : 1;
-    return on && d.precision == 3 && d.dY16 && d.X16 && !d.dbias && (d.Nout & 7) == 0 && (d.Cin & 7) == 0 && (d.ldy & 7) == 0 && (d.ldx & 7) == 0 &&
+    return d.precision == 3 && d.dY16 && d.X16 && !d.dbias && (d.Nout & 7) == 0 && (d.Cin & 7) == 0 && (d.ldy & 7) == 0 && (d.ldx & 7) == 0 &&
            (d.sY & 7) == 0 && (d.sX & 7) == 0 && (d.sY2 & 7) == 0 && (d.sX2 & 7) == 0 && aligned16(d.dY16) && aligned16(d.X16) && d.Nout >= 8 && d.Cin >= 8;
 }
-// 32-pixel blocks per staged k-tile of the twin-fed kernels (wgrad_tr16_body's KP): CDETR_WGRAD_KP = 1 / 2 / 4 (A/B knob, read per call by the tools)
+// 32-pixel blocks per staged k-tile of the twin-fed kernels (wgrad_tr16_body's KP): CDETR_WGRAD_KP = 1 / 2 / 4 (A/B knob, read per call by the tests and tools)
 int wgrad_kp() {
-    static const int kp_env = getenv("CDETR_WGRAD_KP") ? atoi(getenv("CDETR_WGRAD_KP")) : 1;
     const char* e = cdetr_tune_env("CDETR_WGRAD_KP");
-    const int kp = e ? atoi(e) : kp_env;      // (default 1: see profiles/r5_ab_wgrad_kp.txt)
+    const int kp = e ? atoi(e) : 1;      // (default 1: see profiles/r5_ab_wgrad_kp.txt)
     return kp >= 4 ? 4 : kp >= 2 ? 2 : 1;
 }
 bool wgrad_is_fast(const cdetr_wgrad_desc& d) { return (d.ldy & 3) == 0 && (d.ldx & 3) == 0 && (d.Nout & 3) == 0 && (d.Cin & 3) == 0; }
@@ -2405,13 +2391,12 @@ extern "C" int cdetr_wgrad(const cdetr_wgrad_desc* dp, void* stream) {
             constexpr int BI = decltype(bi_c)::value, BJ = decltype(bj_c)::value;
             const int tilesI = (d.Nout + BI - 1) / BI, tilesJ = (d.Cin + BJ - 1) / BJ;
             const long base = (long)tilesI * tilesJ * d.taps * d.batch;
-            static const long target_env = getenv("CDETR_WGRAD_TARGET") ? atol(getenv("CDETR_WGRAD_TARGET")) : 0;
             // ~3 workgroups per CU; weights of <= 16 tiles pay slices x (atomic epilogue + pipeline fill) for little parallelism
             // gained: half as many slices measured 10-15 % faster there (5000x256x256, 20000x512x128)
             // (round 5: 384 for every problem -- beside the data-gradient chain fewer, longer workgroups disturb it less: profiles/r5_ab_wgrad.txt)
             // round 6: wg_target == 0 is again the rule for a launch that has the chip to itself (768; 384 for weights of <= 16
             // tiles); a caller that runs the launch BESIDE a data-gradient chain asks for 384 itself (engine.Trainer: ops.wgrad_flush(wg_target=))
-            const long target = d.wg_target > 0 ? d.wg_target : (target_env ? target_env : (base <= 16 ? 384 : 768));
+            const long target = d.wg_target > 0 ? d.wg_target : (base <= 16 ? 384 : 768);
             long slices = (target + base - 1) / base;
             const long max_slices = (nktf + 3) / 4;                 // >= 4 k-tiles (128 pixels) per slice
             if (slices > max_slices) slices = max_slices;
@@ -2427,8 +2412,7 @@ extern "C" int cdetr_wgrad(const cdetr_wgrad_desc* dp, void* stream) {
                     constexpr int KP = decltype(kp_c)::value;
                     const int tbytes = 2 * ((BI + BJ) / 32) * (KP * 32 * 32 + 32) * 2;   // two buffers of hi planes (padded blocks)
                     if ((rcf = raise_lds(wgrad_tr16_kernel<BI, BJ, KP>, tbytes, "cdetr_wgrad"))) return;
-                    static const int xcd16 = getenv("CDETR_WGRAD_XCD16") ? atoi(getenv("CDETR_WGRAD_XCD16")) : 1;
-                    if (xcd16 && d.batch == 1 && slices >= 8 && max_slices >= 8) {      // XCD-aware slices: a multiple of 8 of them, 1-D grid
+                    if (d.batch == 1 && slices >= 8 && max_slices >= 8) {      // XCD-aware slices: a multiple of 8 of them, 1-D grid
                         long s8 = std::min<long>((slices + 7) / 8 * 8, max_slices / 8 * 8);
                         if (s8 < 8) s8 = 8;
                         const int per8 = (int)((nktf + s8 - 1) / s8);
@@ -2523,7 +2507,6 @@ extern "C" int cdetr_wgrad(const cdetr_wgrad_desc* dp, void* stream) {
 extern "C" int cdetr_wgrad_group(const cdetr_wgrad_desc* descs, int32_t n, void* stream) {
     CDETR_CHECK_ARG(n >= 0 && (descs != nullptr || n == 0), "cdetr_wgrad_group: bad arguments");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const int grouping = getenv("CDETR_WGRAD_GROUP") ? atoi(getenv("CDETR_WGRAD_GROUP")) : 1;
     const char* wfg = cdetr_tune_env("CDETR_WGRAD_VARIANT");
     const bool forced = wfg && atoi(wfg) != 0;
     std::vector<int> direct, tr64p, tr64t;                    // tr64t: the same class with bf16 twins (wgrad_tr16_group_kernel)
@@ -2531,8 +2514,8 @@ extern "C" int cdetr_wgrad_group(const cdetr_wgrad_desc* descs, int32_t n, void*
         const cdetr_wgrad_desc& d = descs[i];
         if (int rcv = check_wgrad_desc(d)) return rcv;
         if (d.P == 0) continue;
-        if (grouping && wgrad_is_direct(d)) direct.push_back(i);
-        else if (grouping && wgrad_is_fast(d) && d.precision >= 1 && !forced &&
+        if (wgrad_is_direct(d)) direct.push_back(i);
+        else if (wgrad_is_fast(d) && d.precision >= 1 && !forced &&
                  !(d.taps > 1 && d.Nout >= 512 && d.Cin >= 512) && !(d.taps == 1 && (long)d.Nout * d.Cin >= (1L << 20) && d.Cin >= 128))
             (wgrad_has_twins(d) ? tr64t : tr64p).push_back(i);      // = the shapes cdetr_wgrad gives to wgrad_tr_kernel<64, 64>
         else if (int rc1 = cdetr_wgrad(&d, stream)) return rc1;
@@ -2567,10 +2550,9 @@ extern "C" int cdetr_wgrad_group(const cdetr_wgrad_desc* descs, int32_t n, void*
             work += (long)((d.Nout + 63) / 64) * ((d.Cin + 63) / 64) * d.taps * d.batch * ((d.P + 31) / 32);
         }
         // 768 for a launch alone on the chip; launches beside the data-gradient chain ask for 384 through wg_target (profiles/r5_ab_wgrad.txt)
-        static const long gtarget = getenv("CDETR_WGRAD_GROUP_TARGET") ? atol(getenv("CDETR_WGRAD_GROUP_TARGET")) : 768;
         long want = 0;                                    // cdetr_wgrad_desc.wg_target: the largest request of the members (a launch alone on the chip)
         for (int k = 0; k < m; ++k) want = std::max<long>(want, descs[tr64[c0 + k]].wg_target);
-        const long gt = want > 0 ? want : gtarget;
+        const long gt = want > 0 ? want : 768;
         long per_all = (work + gt - 1) / gt;
         if (per_all < 4) per_all = 4;
         for (int k = 0; k < m; ++k) {
@@ -2580,8 +2562,7 @@ extern "C" int cdetr_wgrad_group(const cdetr_wgrad_desc* descs, int32_t n, void*
             it.tilesI = (it.d.Nout + 63) / 64; it.tilesJ = (it.d.Cin + 63) / 64;
             it.per = (int)std::min<long>(per_all, nkt);
             it.nx = it.tilesI * it.tilesJ * it.d.taps; it.ny = (nkt + it.per - 1) / it.per; it.pad_ = 0;
-            static const int xcd16 = getenv("CDETR_WGRAD_XCD16") ? atoi(getenv("CDETR_WGRAD_XCD16")) : 1;
-            if (twins && xcd16 && it.d.batch == 1 && it.ny >= 6 && (nkt + 3) / 4 >= 8) {      // XCD-aware slices: a multiple of 8 (see wgrad_tr16_kernel)
+            if (twins && it.d.batch == 1 && it.ny >= 6 && (nkt + 3) / 4 >= 8) {      // XCD-aware slices: a multiple of 8 (see wgrad_tr16_kernel)
                 it.ny = (it.ny + 7) / 8 * 8;
                 it.per = (nkt + it.ny - 1) / it.ny;
                 it.pad_ = 1;

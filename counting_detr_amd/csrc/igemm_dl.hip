@@ -670,20 +670,17 @@ int cdetr_gemm_dl_launch(const cdetr_gemm_desc& d, int tile, int stages, hipStre
         cdetr_set_error("cdetr_gemm (direct-to-LDS, split reduction): no kernel for tile %d with stages code %d", tile, stages);
         return CDETR_ERR_UNSUPPORTED;
     }
-    static const bool late = getenv("CDETR_DL_LATE_EPILOGUE") != nullptr;       // A/B: epilogue operands fetched after the k-loop (round 3)
+    // (epilogue operands are requested ahead of the k-loop; fetched after it -- round 3's form, EARLY = false, which the split forms keep -- the
+    // sweep took 391 against 378 us and the step was neutral: profiles/r4_ab_epilogue_touch.txt, r4_ab_hoist.txt)
     if (stages >= 100) {                                        // phase probe (tools/dl_probe.py): splitk_ws receives the time stamps
         if (!d.splitk_ws) { cdetr_set_error("cdetr_gemm_dl: the phase probe writes into splitk_ws"); return CDETR_ERR_ARG; }
-#define DL_PROBE(FM, FN)                                                                                                  \
-    return late ? (x3 ? launch_dl<FM, FN, 3, 3, true, false>(d, st) : launch_dl<FM, FN, 1, 3, true, false>(d, st))         \
-                : (x3 ? launch_dl<FM, FN, 3, 3, true>(d, st) : launch_dl<FM, FN, 1, 3, true>(d, st))
+#define DL_PROBE(FM, FN) return x3 ? launch_dl<FM, FN, 3, 3, true>(d, st) : launch_dl<FM, FN, 1, 3, true>(d, st)
         if (tile == 0 && stages == 103) { DL_PROBE(2, 2); }
         if (tile == 3 && stages == 103) { DL_PROBE(1, 1); }
         if (tile == 1 && stages == 103) { DL_PROBE(2, 1); }
 #undef DL_PROBE
     }
-#define DL_GO(FM, FN, S)                                                                                            \
-    return late ? (x3 ? launch_dl<FM, FN, 3, S, false, false>(d, st) : launch_dl<FM, FN, 1, S, false, false>(d, st)) \
-                : (x3 ? launch_dl<FM, FN, 3, S>(d, st) : launch_dl<FM, FN, 1, S>(d, st))
+#define DL_GO(FM, FN, S) return x3 ? launch_dl<FM, FN, 3, S>(d, st) : launch_dl<FM, FN, 1, S>(d, st)
     switch (tile * 8 + stages) {
         case 0 * 8 + 2: DL_GO(2, 2, 2);
         case 0 * 8 + 3: DL_GO(2, 2, 3);

@@ -260,19 +260,7 @@ __device__ __forceinline__ unsigned dpp_min_u32(unsigned x) {
 }
 // lexicographic minimum of (val, key) over the wave, returned in every lane: first the minimum value (DPP butterfly inside the
 // rows of 16, row_bcast across them, lane 63 holds the result), then the minimum key among the lanes that hold that value
-template <bool DPP>
 __device__ __forceinline__ void wave_lexmin(double& val, unsigned& key) {
-    if constexpr (!DPP) {          // A/B reference: butterfly over ds_bpermute
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            const double ov = __shfl_xor(val, m, 64);
-            const unsigned ok = (unsigned)__shfl_xor((int)key, m, 64);
-            const bool take = (ov < val) | ((ov == val) & (ok < key));
-            val = take ? ov : val;
-            key = take ? ok : key;
-        }
-        return;
-    }
     double m = val;
     m = dpp_min_f64<0xB1, 0xf>(m);       // quad_perm [1,0,3,2]
     m = dpp_min_f64<0x4E, 0xf>(m);       // quad_perm [2,3,0,1]
@@ -292,15 +280,15 @@ __device__ __forceinline__ void wave_lexmin(double& val, unsigned& key) {
     val = gmin;
 }
 
-template <int CPL, bool COST_LDS, bool DPP = true>
+template <int CPL, bool COST_LDS>
 __global__ __launch_bounds__(64) void lsap_wave_kernel(const float* __restrict__ cost_all, const int64_t* __restrict__ cost_off,
                                                        const int* __restrict__ tgt_off, int Q, int Mmax,
                                                        int64_t* __restrict__ idx_i, int64_t* __restrict__ idx_j,
-                                                       int* __restrict__ status, int prio) {
+                                                       int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     // one wave on the step's critical path, possibly sharing its SIMD with throughput work of another stream (the trainer runs the next
     // batch's frozen stage beside the solve): highest wave priority at the instruction arbiter
-    if (prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     const int b = blockIdx.x;
     const int T = tgt_off[b + 1] - tgt_off[b];
     const bool transpose = T < Q;
@@ -408,7 +396,7 @@ __global__ __launch_bounds__(64) void lsap_wave_kernel(const float* __restrict__
             }
             const double my_val = bval;
             const unsigned my_key = bkey;
-            wave_lexmin<DPP>(bval, bkey);
+            wave_lexmin(bval, bkey);
             if (bkey != 0xffffffffu && bval != INFINITY && (bkey & 0x80000000u) == 0u) {
                 const bool mine = (my_key == bkey) && (my_val == bval);
                 const int wl = __builtin_ctzll(__ballot(mine));
@@ -459,7 +447,7 @@ __global__ __launch_bounds__(64) void lsap_wave_kernel(const float* __restrict__
             }
             const double my_val = bval;
             const unsigned my_key = bkey;
-            wave_lexmin<DPP>(bval, bkey);
+            wave_lexmin(bval, bkey);
             if (bkey == 0xffffffffu || bval == INFINITY) { sink = -2; break; }
             min_val = bval;
             // keys are unique among candidates: exactly one lane owns the winning pair
@@ -605,7 +593,7 @@ __global__ __launch_bounds__(1024) void lsap_wg_kernel(const float* __restrict__
     auto wg_lexmin = [&](double& bval, unsigned& bkey, int best_c, int& jstar, int& rnext, bool& mine) __attribute__((always_inline)) {
         const double my_val = bval;
         const unsigned my_key = bkey;
-        wave_lexmin<true>(bval, bkey);
+        wave_lexmin(bval, bkey);
         const bool wmine = (my_key == bkey) && (my_val == bval) && (bkey != 0xffffffffu);
         const unsigned long long bal = __ballot(wmine);
         const int wl = bal ? __builtin_ctzll(bal) : 0;
@@ -804,23 +792,17 @@ extern "C" int cdetr_lsap(const float* cost, const int64_t* cost_off, const int3
         // single-wave register-resident solver; nr <= Mmax rows, nc <= nc_max columns
         const size_t state = (size_t)Mmax * 12 + (size_t)nc_max * 12 + 64;
         const size_t with_cost = state + (size_t)Mmax * nc_max * 4;
-        static const int lds_env = getenv("CDETR_LSAP_COST_LDS") ? atoi(getenv("CDETR_LSAP_COST_LDS")) : 1;      // A/B: 0 = cost matrix read from L2 (small LDS footprint)
-        const bool cost_lds = lds_env && with_cost <= 156 * 1024;
+        // the cost matrix in LDS when it fits, else read from L2 (isolated, the solve dispatches with no delay whatever its LDS footprint: profiles/r6_step_gaps.txt)
+        const bool cost_lds = with_cost <= 156 * 1024;
         const size_t wb = cost_lds ? with_cost : state;
         auto go = [&](auto kern) {
             if (wb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wb);
-            static const int prio = getenv("CDETR_LSAP_PRIO") ? atoi(getenv("CDETR_LSAP_PRIO")) : 1;      // A/B: s_setprio 3 in the solve
-            hipLaunchKernelGGL(kern, dim3(B), dim3(64), wb, st, cost, cost_off, tgt_off, Q, Mmax, idx_i, idx_j, status, prio);
+            hipLaunchKernelGGL(kern, dim3(B), dim3(64), wb, st, cost, cost_off, tgt_off, Q, Mmax, idx_i, idx_j, status);
         };
         // columns per lane = ceil(nc_max / 64): the per-iteration column scan is unrolled exactly that far
         if (nc_max <= 128) { if (cost_lds) go(lsap_wave_kernel<2, true>); else go(lsap_wave_kernel<2, false>); }
         else if (nc_max <= 256) { if (cost_lds) go(lsap_wave_kernel<4, true>); else go(lsap_wave_kernel<4, false>); }
-        else if (nc_max <= 320) {
-            static const bool shfl = getenv("CDETR_LSAP_SHFL") != nullptr;      // A/B knob: arg-min over ds_bpermute instead of DPP
-            if (cost_lds && shfl) go(lsap_wave_kernel<5, true, false>);
-            else if (cost_lds) go(lsap_wave_kernel<5, true>);
-            else go(lsap_wave_kernel<5, false>);
-        }
+        else if (nc_max <= 320) { if (cost_lds) go(lsap_wave_kernel<5, true>); else go(lsap_wave_kernel<5, false>); }
         else if (nc_max <= 512) { if (cost_lds) go(lsap_wave_kernel<8, true>); else go(lsap_wave_kernel<8, false>); }
         else { if (cost_lds) go(lsap_wave_kernel<16, true>); else go(lsap_wave_kernel<16, false>); }
         return cdetr_launch_status("cdetr_lsap");

@@ -772,23 +772,22 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 extern "C" int cdetr_mha_fwd(const float* qk, const float* v, float* o, float* lse, int32_t N, int32_t L, int32_t nh, float scale,
                              int32_t precision, void* stream) {
     CDETR_CHECK_ARG(qk && v && o && lse && N > 0 && L > 0 && nh > 0, "cdetr_mha_fwd: bad args");
-    static const int use_mfma = getenv("CDETR_MHA_MFMA") ? atoi(getenv("CDETR_MHA_MFMA")) : 1;
-    static const int key_split = getenv("CDETR_MHA_KEY_SPLIT") ? atoi(getenv("CDETR_MHA_KEY_SPLIT")) : 1;      // A/B: 0 = two waves walk all key tiles
     const long E = (long)nh * D;
     const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
-    const bool mfma = use_mfma && precision == 1;
-    launch_fwd(a, o, lse, mfma, mfma && key_split && L >= 128, reinterpret_cast<hipStream_t>(stream));
+    // the keys of a query tile cut in two (fwd_ks_kernel) from 128 keys on; two waves walking all key tiles cost the step 0.03 ms in three of three
+    // rounds (profiles/r5_ab_tail_wgrad.txt)
+    const bool mfma = precision == 1;
+    launch_fwd(a, o, lse, mfma, mfma && L >= 128, reinterpret_cast<hipStream_t>(stream));
     return cdetr_launch_status("cdetr_mha_fwd");
 }
 
 extern "C" int cdetr_mha_bwd(const float* qk, const float* v, const float* o, const float* d_o, const float* lse, float* d_qk,
                              float* d_v, float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision, void* stream) {
     CDETR_CHECK_ARG(qk && v && o && d_o && lse && d_qk && d_v && work && N > 0 && L > 0 && nh > 0, "cdetr_mha_bwd: bad args");
-    static const int use_mfma = getenv("CDETR_MHA_MFMA") ? atoi(getenv("CDETR_MHA_MFMA")) : 1;
     const long E = (long)nh * D;
     const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
     // precision 3: split-bf16 scores, plain-bf16 gradient contractions (flash::bwd_q_body); 1: split-bf16 throughout; else fp32
-    const int tb = (use_mfma && precision == 3) ? 1 : (use_mfma && precision == 1) ? 3 : 0;
+    const int tb = precision == 3 ? 1 : precision == 1 ? 3 : 0;
     launch_bwd(a, o, d_o, lse, d_qk, 2 * E, d_qk + E, 2 * E, d_v, E, work, tb, false, reinterpret_cast<hipStream_t>(stream));
     return cdetr_launch_status("cdetr_mha_bwd");
 }
@@ -799,11 +798,7 @@ extern "C" int cdetr_mha_bwd(const float* qk, const float* v, const float* o, co
 // of waves, and halving each wave's chain of key tiles wins at every size the variant meets.  The backward's one launch (bwd_kernel, grid
 // as wide as the longer side) against two exactly sized launches: 300 x 864 81 vs 98 us, 900 x 2500 190 vs 234, 2500 x 2500 385 vs 478 --
 // one launch lets the query and key halves share the chip.
-static bool attn_key_split(int Lk) {
-    static const int force = getenv("CDETR_ATTN_KEY_SPLIT") ? atoi(getenv("CDETR_ATTN_KEY_SPLIT")) : -1;     // A/B: 0 / 1 forces the choice
-    if (force >= 0) return force != 0;
-    return Lk >= 128;
-}
+static bool attn_key_split(int Lk) { return Lk >= 128; }
 
 static int attn_check(const cdetr_attn_desc* d, const char* what) {
     CDETR_CHECK_ARG(d && d->q && d->k && d->v && d->o && d->lse && d->N > 0 && d->Lq > 0 && d->Lk > 0 && d->nh > 0, "%s: bad args", what);

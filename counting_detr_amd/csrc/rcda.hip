@@ -359,7 +359,6 @@ __global__ __launch_bounds__(64 * NW) void rcda_fwd_kernel(const cdetr_rcda_fwd_
 //     per-lane scalar (the form with A_col*A_row as the MFMA operand needs a multiply + bf16 split per element per h);
 //   * V tiles are prefetched PD = 4 iterations ahead (8 registers per tile per thread): an iteration is never bound by
 //     the global-load latency, which is what limited the one-tile-ahead pipeline of rcda_fwd_kernel.
-constexpr int RCDA_RG_DEFAULT = 1;       // key rows per barrier of the two-step forward (see rcda_fwd2_kernel, RG)
 constexpr int RCDA_WS_COUNTERS = 4096;   // int32 arrival counters at the head of cdetr_rcda_fwd_desc.ws (= SPLITK_COUNTERS of igemm.hip: one scratch serves both)
 constexpr int KSTR = 36;      // LDS row stride (floats) of the projected keys in rcda_scores_mfma: 36 / 4 odd -> conflict-free ds_read_b128
 
@@ -510,11 +509,11 @@ __device__ __forceinline__ void rcda_scores_mfma(const cdetr_rcda_fwd_desc& d, c
 }
 
 struct Fwd2Smem { int off_v, vts, total; };
-__host__ __device__ inline Fwd2Smem fwd2_smem(const FwdSmem& sm, int H, int W, int KS, int RG = 1) {
+__host__ __device__ inline Fwd2Smem fwd2_smem(const FwdSmem& sm, int H, int W, int KS) {
     Fwd2Smem s;
     s.off_v = sm.off_k;
     s.vts = 32 * KS + 8;                                   // bf16 per V^T row: [hi 16KS | lo 16KS | pad 8] -> odd multiple of 16 bytes
-    const int vfloats = 2 * RG * 32 * s.vts / 2;           // two buffers (RG = 2: two PAIRS of buffers) of 32 channel rows
+    const int vfloats = 2 * 32 * s.vts / 2;                // two buffers of 32 channel rows
     const int kfloats = (W + H) * KSTR;                    // key tiles of the score phase, padded rows (see rcda_scores_mfma)
     s.total = sm.off_k + (kfloats > vfloats ? kfloats : vfloats);
     return s;
@@ -523,11 +522,11 @@ __host__ __device__ inline Fwd2Smem fwd2_smem(const FwdSmem& sm, int H, int W, i
 // PROBE (tools/rcda_probe.py, CDETR_RCDA_PROBE=1; never dispatched otherwise): every wave writes 16 x uint64 of s_memtime readings into
 // cdetr_rcda_fwd_desc.ws -- [kernel start, score phase done, main loop start, main loop end, output stored, cycles spent waiting at the
 // per-key-row barrier, cycles in the MFMA + accumulate section, cycles in fetch + stash] -- so that "barrier cadence" is a number.
-// RG = 2 (round 6): TWO key rows per workgroup barrier -- four LDS tile buffers (two pairs), the rows' MFMA chains T_h and T_h+1 are
-// independent and interleave, half as many barriers.  The phase probe of the RG = 1 loop at the encoder shape (profiles/r6_rcda_probe.txt):
-// per key row ~650 cycles in the MFMA + accumulate section (12 dependent MFMAs = 384 cycles of issue), ~390 in fetch + stash, ~370 waiting
-// at the barrier.
-template <int NW, int KS, int TH = 2, bool PROBE = false, int RG = 1>   // KS = 16-column steps of the key axis W (W <= 16 KS <= 96); TH = 32-row tiles of H in the MFMA score phase
+// One key row per workgroup barrier.  The phase probe of this loop at the encoder shape (profiles/r6_rcda_probe.txt): per key row ~650 cycles
+// in the MFMA + accumulate section (12 dependent MFMAs = 384 cycles of issue), ~390 in fetch + stash, ~370 waiting at the barrier.  (Round 6,
+// measured and dropped: TWO key rows per barrier -- four LDS tile buffers, the rows' MFMA chains interleaved, half as many barriers: nothing
+// un-instrumented, profiles/r6_ab_rcda_rg.txt.)
+template <int NW, int KS, int TH = 2, bool PROBE = false>   // KS = 16-column steps of the key axis W (W <= 16 KS <= 96); TH = 32-row tiles of H in the MFMA score phase
 __global__ __launch_bounds__(64 * NW) void rcda_fwd2_kernel(const cdetr_rcda_fwd_desc d) {
     unsigned long long pt[5] = {0, 0, 0, 0, 0}, pacc[3] = {0, 0, 0};
     auto now = [&]() __attribute__((always_inline)) -> unsigned long long {
@@ -630,7 +629,6 @@ __global__ __launch_bounds__(64 * NW) void rcda_fwd2_kernel(const cdetr_rcda_fwd
 
     vfetch(rv[0]); vfetch(rv[1]); vfetch(rv[2]); vfetch(rv[3]);
     vstash(rv[0], 0);          // the K tiles this overlays are dead: rcda_scores ended with a barrier
-    if constexpr (RG == 2) vstash(rv[1], 1);
     __syncthreads();
     // one iteration; U = h mod PD is a compile-time constant so the register ring is statically indexed
     pt[2] = now();
@@ -660,52 +658,11 @@ __global__ __launch_bounds__(64 * NW) void rcda_fwd2_kernel(const cdetr_rcda_fwd
             pacc[0] += s4 - s3; pacc[1] += s2 - s1; pacc[2] += (s1 - s0) + (s3 - s2);
         }
     };
-    // RG == 2: pair P = (h / 2) mod 2 owns LDS buffers 2P, 2P + 1 and register sets 2P, 2P + 1
-    auto step2 = [&](auto P_, int h) __attribute__((always_inline)) {
-        constexpr int P = decltype(P_)::value, Q = 1 - P;
-        const unsigned long long s0 = now();
-        vfetch(rv[2 * P]);                                               // tiles h + 4, h + 5; the sets were stashed one iteration ago
-        vfetch(rv[2 * P + 1]);
-        const unsigned long long s1 = now();
-        const float acol0 = (h < he) ? Scol[i32 * sm.sh + h] : 0.f;
-        const float acol1 = (h + 1 < he) ? Scol[i32 * sm.sh + h + 1] : 0.f;
-        const __bf16* vt0 = VT + (2 * P) * 32 * VTS + i32 * VTS + 8 * g;
-        const __bf16* vt1 = vt0 + 32 * VTS;
-        f32x16 T0 = zero, T1 = zero;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const bf16x8 ah0 = *reinterpret_cast<const bf16x8*>(vt0 + 16 * s);
-            const bf16x8 al0 = *reinterpret_cast<const bf16x8*>(vt0 + 16 * KS + 16 * s);
-            const bf16x8 ah1 = *reinterpret_cast<const bf16x8*>(vt1 + 16 * s);
-            const bf16x8 al1 = *reinterpret_cast<const bf16x8*>(vt1 + 16 * KS + 16 * s);
-            T0 = mfma_bf16x3(ah0, al0, bh[s], bl[s], T0);
-            T1 = mfma_bf16x3(ah1, al1, bh[s], bl[s], T1);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) outT[r] = fmaf(acol1, T1[r], fmaf(acol0, T0[r], outT[r]));
-        unsigned long long s2 = 0;
-        if constexpr (PROBE) { asm volatile("" :: "v"(outT[0]), "v"(outT[15])); s2 = now(); }
-        vstash(rv[2 * Q], 2 * Q);                                        // tiles h + 2, h + 3 -> the pair tiles h - 2, h - 1 used
-        vstash(rv[2 * Q + 1], 2 * Q + 1);
-        const unsigned long long s3 = now();
-        __syncthreads();
-        if constexpr (PROBE) {
-            const unsigned long long s4 = now();
-            pacc[0] += s4 - s3; pacc[1] += s2 - s1; pacc[2] += (s1 - s0) + (s3 - s2);
-        }
-    };
-    if constexpr (RG == 2) {
-        for (int h0 = hb; h0 < he; h0 += 4) {
-            step2(std::integral_constant<int, 0>{}, h0);
-            step2(std::integral_constant<int, 1>{}, h0 + 2);
-        }
-    } else {
-        for (int h0 = hb; h0 < he; h0 += PD) {
-            step(std::integral_constant<int, 0>{}, h0);
-            step(std::integral_constant<int, 1>{}, h0 + 1);
-            step(std::integral_constant<int, 2>{}, h0 + 2);
-            step(std::integral_constant<int, 3>{}, h0 + 3);
-        }
+    for (int h0 = hb; h0 < he; h0 += PD) {
+        step(std::integral_constant<int, 0>{}, h0);
+        step(std::integral_constant<int, 1>{}, h0 + 1);
+        step(std::integral_constant<int, 2>{}, h0 + 2);
+        step(std::integral_constant<int, 3>{}, h0 + 3);
     }
     pt[3] = now();
     if (hs > 1) {
@@ -772,9 +729,6 @@ __global__ __launch_bounds__(64 * NW) void rcda_fwd2_kernel(const cdetr_rcda_fwd
 //   U: per-wave [32][su] slices holding A_col at the start and the ds_col / A_row staging at the end; while the main loop
 //      runs (A_col lives in registers) the same memory is the double-buffered V tile shared by the workgroup;
 //   R: per-wave [32][sw] A_row; element (q, w) is overwritten by dA_row[q, w] as soon as column w has been consumed.
-// A/B knob of the fused key gradients (rcda_bwd_body): 1 = every wave adds its partial tiles to global itself (rounds 3-5)
-__device__ __constant__ int g_rcda_dk_per_wave = 0;
-__device__ __forceinline__ bool rcda_dk_per_wave() { return g_rcda_dk_per_wave != 0; }
 constexpr int BWD_CG = 2;     // key columns staged and consumed per workgroup barrier of the dS kernel
 struct BwdSmem {
     int sw, sh, su, off_u, off_r, off_kk, total;
@@ -1153,8 +1107,8 @@ __device__ __forceinline__ void rcda_bwd_body(const cdetr_rcda_bwd_desc& d, cons
                 // Round 6: the waves' partial [keys][32] tiles meet in LDS (each wave parks its two tiles in its own, by then dead, dS slices) and
                 // the workgroup adds ONE tile per side to global: NW x fewer atomics (the probe put 11 us of the encoder-shape workgroup's 55 us
                 // into this phase: 80 waves per (image, head) adding to the same 6400 addresses).  Maps with more than 128 keys per side keep the
-                // per-wave atomics.
-                const bool wg_reduce = (W <= 128 && H <= 128) && !rcda_dk_per_wave();
+                // per-wave atomics (at the encoder shape they made the dS kernel 96.3-97.3 us against 86.3).
+                const bool wg_reduce = W <= 128 && H <= 128;
                 constexpr int NTL = 4;
 #pragma unroll
                 for (int side = 0; side < 2; ++side) {
@@ -1569,8 +1523,9 @@ int set_smem(F func, int bytes, const char* what) {
     return CDETR_OK;
 }
 
-template <int NF, int NW>
+template <int NF>
 int launch_rcda_fwd(const cdetr_rcda_fwd_desc& d, hipStream_t st) {
+    constexpr int NW = 4;
     const FwdSmem sm = fwd_smem(d.H, d.W, NW);
     const int bytes = sm.total * 4;
     int rc;
@@ -1584,40 +1539,56 @@ int launch_rcda_fwd(const cdetr_rcda_fwd_desc& d, hipStream_t st) {
     }
     return cdetr_launch_status("cdetr_rcda_fwd");
 }
-// hgroups > 0: the two-step dV of the same attention (hgroups x slices workgroups, `per` queries per slice) rides in the same launch
+// dS and the two-step dV of the same attention in ONE launch (hgroups x slices dV workgroups, `per` queries per slice, behind the dS grid):
+// every split-bf16 shape with H <= 64
 template <int NF, int NW>
-int launch_rcda_bwd(const cdetr_rcda_bwd_desc& d, hipStream_t st, int hgroups = 0, int slices = 0, int per = 0) {
+int launch_rcda_bwd_all(const cdetr_rcda_bwd_desc& d, hipStream_t st, int hgroups, int slices, int per) {
+    const int bytes = std::max(bwd_smem(d.H, d.W, NF, NW, d.dq_row != nullptr).total * 4, dv2_smem().total * 4);
+    int rc;
+    const int nqb = (d.L + QW * NW - 1) / (QW * NW);
+    dim3 grid(nqb + hgroups * slices, d.N * d.nh);
+    if (d.precision == 3) {          // plain-bf16 products (the backward's arithmetic)
+        if ((rc = set_smem(rcda_bwd_all_kernel<NF, NW, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
+        hipLaunchKernelGGL((rcda_bwd_all_kernel<NF, NW, 1>), grid, dim3(512), bytes, st, d, nqb, hgroups, per);
+    } else {
+        if ((rc = set_smem(rcda_bwd_all_kernel<NF, NW, 3>, bytes, "cdetr_rcda_bwd"))) return rc;
+        hipLaunchKernelGGL((rcda_bwd_all_kernel<NF, NW, 3>), grid, dim3(512), bytes, st, d, nqb, hgroups, per);
+    }
+    return cdetr_launch_status("cdetr_rcda_bwd(dS+dV)");
+}
+// dS alone: fp32 mode, and H > 64 (NF = 4), whose dS kernel needs more than the 256 registers a 512-thread block leaves a wave
+template <int NF, int NW>
+int launch_rcda_bwd(const cdetr_rcda_bwd_desc& d, hipStream_t st) {
     const BwdSmem sm = bwd_smem(d.H, d.W, NF, NW, d.dq_row != nullptr);
-    int bytes = sm.total * 4;
+    const int bytes = sm.total * 4;
     int rc;
     dim3 grid((d.L + QW * NW - 1) / (QW * NW), d.N * d.nh), block(64 * NW);
-    if (hgroups > 0) {
-        bytes = std::max(bytes, dv2_smem().total * 4);
-        const int nqb = grid.x;
-        dim3 g2(nqb + hgroups * slices, d.N * d.nh);
+    if constexpr (NF == 4) {
         if (d.precision == 3) {
-            if ((rc = set_smem(rcda_bwd_all_kernel<NF, NW, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
-            hipLaunchKernelGGL((rcda_bwd_all_kernel<NF, NW, 1>), g2, dim3(512), bytes, st, d, nqb, hgroups, per);
-        } else {
-            if ((rc = set_smem(rcda_bwd_all_kernel<NF, NW, 3>, bytes, "cdetr_rcda_bwd"))) return rc;
-            hipLaunchKernelGGL((rcda_bwd_all_kernel<NF, NW, 3>), g2, dim3(512), bytes, st, d, nqb, hgroups, per);
+            if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 1, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
+            hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 1, 1>), grid, block, bytes, st, d);
+            return cdetr_launch_status("cdetr_rcda_bwd(dS)");
         }
-        return cdetr_launch_status("cdetr_rcda_bwd(dS+dV)");
+        if (d.precision >= 1) {
+            if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
+            hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 1>), grid, block, bytes, st, d);
+            return cdetr_launch_status("cdetr_rcda_bwd(dS)");
+        }
     }
-    if (d.precision == 3) {          // plain-bf16 products (the backward's arithmetic)
-        if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 1, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
-        hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 1, 1>), grid, block, bytes, st, d);
-    } else if (d.precision >= 1) {
-        if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 1>, bytes, "cdetr_rcda_bwd"))) return rc;
-        hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 1>), grid, block, bytes, st, d);
-    } else {
-        if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 0>, bytes, "cdetr_rcda_bwd"))) return rc;
-        hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 0>), grid, block, bytes, st, d);
-    }
+    if ((rc = set_smem(rcda_bwd_kernel<NF, NW, 0>, bytes, "cdetr_rcda_bwd"))) return rc;
+    hipLaunchKernelGGL((rcda_bwd_kernel<NF, NW, 0>), grid, block, bytes, st, d);
     return cdetr_launch_status("cdetr_rcda_bwd(dS)");
 }
-// waves per workgroup: 4 (128 queries share every staged V tile).  2-wave workgroups used to pay for the short decoder query
-// sets; with the grouped / prefetched tile loops they no longer do (tools/rcda_bench.py: dS 66 vs 73 us, fwd 50 vs 52 us).
+// Waves per workgroup: 4 (128 queries share every staged V tile), or 5 where rcda_wg5 says so.  2-wave workgroups used to pay for the short
+// decoder query sets; with the grouped / prefetched tile loops they no longer did (tools/rcda_bench.py: dS 66 vs 73 us, fwd 50 vs 52 us) and are gone.
+// 5-wave workgroups (160 queries) when that lands the grid on <= one workgroup per CU and 4 waves do not: the encoder's 2 x 8 x 2500 queries
+// are 320 workgroups of 128 (64 CUs get two) but exactly 256 of 160.
+// (round 6, measured and dropped: 6 / 7 / 8 waves per workgroup at the encoder shape -- two waves per SIMD so that one wave's MFMAs overlap the
+// other's VALU / LDS work, fewer busy CUs: 51.6 / 53.0 / 54.5 us against 49.5 for the 5-wave form; profiles/r6_rcda_probe.txt)
+inline bool rcda_wg5(int L, int NH) {
+    const long wg4 = (long)((L + QW * 4 - 1) / (QW * 4)) * NH, wg5 = (long)((L + QW * 5 - 1) / (QW * 5)) * NH;
+    return wg4 > 256 && wg4 <= 512 && wg5 <= 256;
+}
 // Key-row slices of the two-step forward (gridDim.z of rcda_fwd2_kernel): enough workgroups that every CU holds two (their
 // barrier-separated iterations then overlap), each slice keeping >= 8 key rows; 1 when the caller gave no scratch.
 inline int fwd2_slices(const cdetr_rcda_fwd_desc& d, int base, int nt, int lds_bytes) {
@@ -1636,12 +1607,10 @@ inline int fwd2_slices(const cdetr_rcda_fwd_desc& d, int base, int nt, int lds_b
     while (hs > 1 && (long)base * hs * 16 * nt * 4 > avail) --hs;
     return hs < 1 ? 1 : hs;
 }
-
-inline int pick_nw(int L, int NH) {
-    (void)L; (void)NH;
-    const char* f = cdetr_tune_env("CDETR_RCDA_NW");
-    if (f) return atoi(f) == 2 ? 2 : 4;
-    return 4;
+// tools/rcda_probe.py (CDETR_RCDA_PROBE = 4 | 5 waves, read under CDETR_TUNING): the phase-probe instantiations instead of the product kernels
+inline int rcda_probe() {
+    const char* p = cdetr_tune_env("CDETR_RCDA_PROBE");
+    return p ? atoi(p) : 0;
 }
 
 }  // namespace
@@ -1654,69 +1623,35 @@ extern "C" int cdetr_rcda_fwd(const cdetr_rcda_fwd_desc* dp, void* stream) {
     CDETR_CHECK_ARG(d.q_row && d.q_col && d.k_row && d.k_col && d.v && d.out, "cdetr_rcda_fwd: null pointer");
     CDETR_CHECK_ARG((d.a_row != nullptr) == (d.a_col != nullptr), "cdetr_rcda_fwd: a_row and a_col are saved together or not at all (both NULL: inference)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nw = pick_nw(d.L, d.N * d.nh);
-    static const int use_v2 = getenv("CDETR_RCDA_FWD2") ? atoi(getenv("CDETR_RCDA_FWD2")) : 1;
-    static const int wide = getenv("CDETR_RCDA_WIDE") ? atoi(getenv("CDETR_RCDA_WIDE")) : 1;       // 0: rounds 1-5 (W <= 64 only), for A/B
-    if (use_v2 && d.precision == 1 && d.W <= (wide ? 96 : 64)) {      // two-step form (see rcda_fwd2_kernel); W <= 96 = an 800 x 1333 image (FSCD-LVIS) at stride 16
+    if (d.precision == 1 && d.W <= 96) {      // two-step form (see rcda_fwd2_kernel); W <= 96 = an 800 x 1333 image (FSCD-LVIS) at stride 16
         const int ks = (d.W + 15) / 16;
-        // key rows per barrier (rcda_fwd2_kernel<..., RG>): CDETR_RCDA_RG = 1 | 2
-        static const int rg_env = getenv("CDETR_RCDA_RG") ? atoi(getenv("CDETR_RCDA_RG")) : RCDA_RG_DEFAULT;
-        const char* rg_t = cdetr_tune_env("CDETR_RCDA_RG");
-        const int rg = ((rg_t ? atoi(rg_t) : rg_env) == 2 && ks == 4 && d.H <= 64) ? 2 : 1;
-        auto go = [&](auto kern, int NWv, int KSv = 0, int RGv = 1) -> int {     // KSv: the kernel's KS when it is not ceil(W / 16)
+        auto go = [&](auto kern, int NWv, int KSv = 0, bool sliced = true) -> int {     // KSv: the kernel's KS when it is not ceil(W / 16)
             const FwdSmem sm = fwd_smem(d.H, d.W, NWv);
-            const int bytes = fwd2_smem(sm, d.H, d.W, KSv ? KSv : ks, RGv).total * 4;
+            const int bytes = fwd2_smem(sm, d.H, d.W, KSv ? KSv : ks).total * 4;
             int rc;
             if ((rc = set_smem(kern, bytes, "cdetr_rcda_fwd"))) return rc;
             dim3 grid((d.L + QW * NWv - 1) / (QW * NWv), d.N * d.nh), block(64 * NWv);
-            grid.z = fwd2_slices(d, (int)(grid.x * grid.y), 64 * NWv, bytes);
+            if (sliced) grid.z = fwd2_slices(d, (int)(grid.x * grid.y), 64 * NWv, bytes);
             hipLaunchKernelGGL(kern, grid, block, bytes, st, d);
             return cdetr_launch_status("cdetr_rcda_fwd");
         };
-        // 5-wave workgroups (160 queries) when that lands the grid on <= one workgroup per CU and 4 waves do not: the encoder's
-        // 2 x 8 x 2500 queries are 320 workgroups of 128 (64 CUs get two) but exactly 256 of 160
-        static const int probe = getenv("CDETR_RCDA_PROBE") ? atoi(getenv("CDETR_RCDA_PROBE")) : 0;
-        if (probe && d.ws && ks == 4 && d.H <= 64) {     // tools/rcda_probe.py: unsliced launch, stamps into d.ws
-            auto gop = [&](auto kern, int NWv) -> int {
-                const FwdSmem sm = fwd_smem(d.H, d.W, NWv);
-                const int bytes = fwd2_smem(sm, d.H, d.W, ks, rg).total * 4;
-                int rc;
-                if ((rc = set_smem(kern, bytes, "cdetr_rcda_fwd"))) return rc;
-                dim3 grid((d.L + QW * NWv - 1) / (QW * NWv), d.N * d.nh), block(64 * NWv);
-                hipLaunchKernelGGL(kern, grid, block, bytes, st, d);
-                return cdetr_launch_status("cdetr_rcda_fwd(probe)");
-            };
-            if (rg == 2) return probe == 5 ? gop(rcda_fwd2_kernel<5, 4, 2, true, 2>, 5) : gop(rcda_fwd2_kernel<4, 4, 2, true, 2>, 4);
-            return probe == 5 ? gop(rcda_fwd2_kernel<5, 4, 2, true>, 5) : gop(rcda_fwd2_kernel<4, 4, 2, true>, 4);
-        }
-        static const int nw5_env = getenv("CDETR_RCDA_NW5") ? atoi(getenv("CDETR_RCDA_NW5")) : 1;
-        const char* nw5_t = cdetr_tune_env("CDETR_RCDA_NW5");
-        const int nw5 = nw5_t ? atoi(nw5_t) : nw5_env;
-        const long wg4 = (long)((d.L + QW * 4 - 1) / (QW * 4)) * d.N * d.nh, wg5 = (long)((d.L + QW * 5 - 1) / (QW * 5)) * d.N * d.nh;
-        // (round 6, measured and dropped: 6 / 7 / 8 waves per workgroup at the encoder shape -- two waves per SIMD so that one wave's MFMAs overlap the
-        // other's VALU / LDS work, fewer busy CUs: 51.6 / 53.0 / 54.5 us against 49.5 for the 5-wave form; profiles/r6_rcda_probe.txt)
-        if (nw5 && nw == 4 && ks == 4 && wg4 > 256 && wg4 <= 512 && wg5 <= 256)
-            return rg == 2 ? go(rcda_fwd2_kernel<5, 4, 2, false, 2>, 5, 0, 2) : go(rcda_fwd2_kernel<5, 4>, 5);
-        if (rg == 2 && nw == 4) return go(rcda_fwd2_kernel<4, 4, 2, false, 2>, 4, 0, 2);
-        if (ks > 4 || (wide && d.H > 64)) {         // wide / tall maps (round 6): a third 32-key tile in the score phase
+        if (const int probe = rcda_probe(); probe && d.ws && ks == 4 && d.H <= 64)     // unsliced launch, stamps into d.ws
+            return probe == 5 ? go(rcda_fwd2_kernel<5, 4, 2, true>, 5, 0, false) : go(rcda_fwd2_kernel<4, 4, 2, true>, 4, 0, false);
+        if (ks == 4 && rcda_wg5(d.L, d.N * d.nh)) return go(rcda_fwd2_kernel<5, 4>, 5);
+        if (ks > 4 || d.H > 64) {         // wide / tall maps (round 6): a third 32-key tile in the score phase
             if (d.H > 64 && d.H <= 96) return ks <= 4 ? go(rcda_fwd2_kernel<4, 4, 3>, 4, 4) : go(rcda_fwd2_kernel<4, 6, 3>, 4, 6);
             if (ks <= 4) return go(rcda_fwd2_kernel<4, 4>, 4, 4);        // H > 96: VALU score phase
             return ks == 5 ? go(rcda_fwd2_kernel<4, 5>, 4) : go(rcda_fwd2_kernel<4, 6>, 4);
         }
-        if (nw == 4) {
-            if (ks == 1) return go(rcda_fwd2_kernel<4, 1>, 4);
-            if (ks == 2) return go(rcda_fwd2_kernel<4, 2>, 4);
-            if (ks == 3) return go(rcda_fwd2_kernel<4, 3>, 4);
-            return go(rcda_fwd2_kernel<4, 4>, 4);
-        }
-        if (ks == 1) return go(rcda_fwd2_kernel<2, 1>, 2);
-        if (ks == 2) return go(rcda_fwd2_kernel<2, 2>, 2);
-        if (ks == 3) return go(rcda_fwd2_kernel<2, 3>, 2);
-        return go(rcda_fwd2_kernel<2, 4>, 2);
+        if (ks == 1) return go(rcda_fwd2_kernel<4, 1>, 4);
+        if (ks == 2) return go(rcda_fwd2_kernel<4, 2>, 4);
+        if (ks == 3) return go(rcda_fwd2_kernel<4, 3>, 4);
+        return go(rcda_fwd2_kernel<4, 4>, 4);
     }
-    if (d.H <= 32) return nw == 4 ? launch_rcda_fwd<1, 4>(d, st) : launch_rcda_fwd<1, 2>(d, st);
-    if (d.H <= 64) return nw == 4 ? launch_rcda_fwd<2, 4>(d, st) : launch_rcda_fwd<2, 2>(d, st);
-    return nw == 4 ? launch_rcda_fwd<4, 4>(d, st) : launch_rcda_fwd<4, 2>(d, st);
+    // fp32 mode, and maps wider than 96 columns
+    if (d.H <= 32) return launch_rcda_fwd<1>(d, st);
+    if (d.H <= 64) return launch_rcda_fwd<2>(d, st);
+    return launch_rcda_fwd<4>(d, st);
 }
 
 extern "C" int cdetr_rcda_bwd(const cdetr_rcda_bwd_desc* dp, void* stream) {
@@ -1733,48 +1668,8 @@ extern "C" int cdetr_rcda_bwd(const cdetr_rcda_bwd_desc* dp, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int NF = d.H <= 32 ? 1 : (d.H <= 64 ? 2 : 4);
     const int Wp = (d.W + 3) & ~3;
-    const int nw = pick_nw(d.L, d.N * d.nh);
     int rc;
-    // the two-step dV (rcda_dv2_kernel) rides in the dS launch (rcda_bwd_all_kernel) unless CDETR_RCDA_MERGE=0
-    static const int use_dv2 = getenv("CDETR_RCDA_DV2") ? atoi(getenv("CDETR_RCDA_DV2")) : 1;
-    static const int merge = getenv("CDETR_RCDA_MERGE") ? atoi(getenv("CDETR_RCDA_MERGE")) : 1;
-    static const int wide = getenv("CDETR_RCDA_WIDE") ? atoi(getenv("CDETR_RCDA_WIDE")) : 1;
-    const bool dv2 = use_dv2 && d.precision >= 1 && (wide || d.W <= 64);
-    int hgroups = 0, slices = 0, per = 0;
-    if (dv2) {
-        hgroups = ((d.H + 7) / 8) * ((Wp + 63) / 64);                // (key-row groups) x (chunks of <= 64 key columns), see rcda_dv2_body
-        const long base = (long)hgroups * d.N * d.nh;
-        // query slices of the dV workgroups.  Round 6 (after the dS kernel got shorter): 2 slices at the encoder shape (224 workgroups: dS + dV 82-83 us;
-        // 4 slices, the rounds 2-5 rule: 85-87; 1 slice: 94-96) and 1 slice when the launch is shared with a short dS grid (decoder: 37.8-38.5 us
-        // against 40.0); CDETR_RCDA_DV2_TARGET overrides
-        static const int dv2_target_env = getenv("CDETR_RCDA_DV2_TARGET") ? atoi(getenv("CDETR_RCDA_DV2_TARGET")) : 0;
-        const long ds_wgs0 = (long)((d.L + QW * nw - 1) / (QW * nw)) * d.N * d.nh;
-        const int dv2_target = dv2_target_env ? dv2_target_env : (ds_wgs0 <= 128 ? 112 : 224);
-        slices = (int)((dv2_target + base - 1) / base);
-        const int max_slices = (d.L + 255) / 256;                    // >= 4 q-tiles per slice
-        if (slices > max_slices) slices = max_slices;
-        if (slices < 1) slices = 1;
-        per = (d.L + slices - 1) / slices;
-        per = ((per + 63) / 64) * 64;
-        slices = (d.L + per - 1) / per;
-    }
-    // (Rounds 2-5 merged only when the dS grid left most CUs free -- decoder: 48 workgroups --, because at the encoder shape 61 + 33 us became
-    // 117 us with the kernels of that time.  The H > 64 kernels need more than the 256 registers a 512-thread block leaves a wave: never merged.)
-    const long ds_wgs = (long)((d.L + QW * nw - 1) / (QW * nw)) * d.N * d.nh;
-    // Round 6: merged at EVERY shape the two-step dV covers.  With the dS body 13 % shorter and the dV workgroups on two query slices the shared
-    // launch now wins at the encoder shape too (dS + dV 82 -> 76.4-77.1 us; 50 x 84 keys, L = 4200: 275 -> 176 us; step -0.02...-0.09 ms in three
-    // same-lease pairs, profiles/r6_ab_rcda_slices.txt) -- the 117 us of round 2 was measured with the round-2 kernels.  CDETR_RCDA_MERGE=3: the old
-    // rule (merge only when the dS grid is <= 128 workgroups), 0: never.
-    const int mh = (dv2 && NF < 4 && (merge == 1 || merge == 2 || (merge == 3 && ds_wgs <= 128))) ? hgroups : 0;
-    static const int dk_per_wave = getenv("CDETR_RCDA_DK_PER_WAVE") ? atoi(getenv("CDETR_RCDA_DK_PER_WAVE")) : 0;      // A/B only
-    static bool dk_pushed = false;
-    if (dk_per_wave && !dk_pushed) {
-        const int one = 1;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rcda_dk_per_wave), &one, sizeof(int));
-        dk_pushed = true;
-    }
-    static const int probe = getenv("CDETR_RCDA_PROBE") ? atoi(getenv("CDETR_RCDA_PROBE")) : 0;
-    if (probe && NF == 2 && d.precision == 3 && d.ds_row && d.dk_row) {      // tools/rcda_probe.py: the dS kernel alone, stamps into ds_row
+    if (const int probe = rcda_probe(); probe && NF == 2 && d.precision == 3 && d.ds_row && d.dk_row) {      // the dS kernel alone, stamps into ds_row
         const int NWp = probe == 5 ? 5 : 4;
         const BwdSmem sm = bwd_smem(d.H, d.W, 2, NWp, true);
         dim3 grid((d.L + QW * NWp - 1) / (QW * NWp), d.N * d.nh), block(64 * NWp);
@@ -1787,17 +1682,32 @@ extern "C" int cdetr_rcda_bwd(const cdetr_rcda_bwd_desc* dp, void* stream) {
         }
         return cdetr_launch_status("cdetr_rcda_bwd(probe)");
     }
-    if (NF == 1) rc = nw == 4 ? launch_rcda_bwd<1, 4>(d, st, mh, slices, per) : launch_rcda_bwd<1, 2>(d, st, mh, slices, per);
-    else if (NF == 2) {
-        // 5-wave workgroups when they put the grid on <= one workgroup per CU and 4-wave ones do not (see cdetr_rcda_fwd)
-        static const int nw5 = getenv("CDETR_RCDA_NW5") ? atoi(getenv("CDETR_RCDA_NW5")) : 1;
-        const long wg4 = (long)((d.L + QW * 4 - 1) / (QW * 4)) * d.N * d.nh, wg5 = (long)((d.L + QW * 5 - 1) / (QW * 5)) * d.N * d.nh;
-        if (nw5 && nw == 4 && wg4 > 256 && wg4 <= 512 && wg5 <= 256) rc = launch_rcda_bwd<2, 5>(d, st, mh, slices, per);
-        else rc = nw == 4 ? launch_rcda_bwd<2, 4>(d, st, mh, slices, per) : launch_rcda_bwd<2, 2>(d, st, mh, slices, per);
-    }
-    else rc = nw == 4 ? launch_rcda_bwd<4, 4>(d, st, mh, slices, per) : launch_rcda_bwd<4, 2>(d, st, mh, slices, per);
-    if (rc || mh) return rc;
-    if (dv2) {   // two-step dV as its own launch
+    // 5-wave workgroups where the forward takes them (rcda_wg5)
+    const bool wg5 = NF == 2 && rcda_wg5(d.L, d.N * d.nh);
+    const bool dv2 = d.precision >= 1;          // the two-step dV (rcda_dv2_kernel); fp32 mode keeps rcda_dv_kernel
+    if (dv2) {
+        const int hgroups = ((d.H + 7) / 8) * ((Wp + 63) / 64);      // (key-row groups) x (chunks of <= 64 key columns), see rcda_dv2_body
+        const long base = (long)hgroups * d.N * d.nh;
+        // query slices of the dV workgroups.  Round 6 (after the dS kernel got shorter): 2 slices at the encoder shape (224 workgroups: dS + dV 82-83 us;
+        // 4 slices, the rounds 2-5 rule: 85-87; 1 slice: 94-96) and 1 slice when the launch is shared with a short dS grid (decoder: 37.8-38.5 us
+        // against 40.0)
+        const long ds_wgs = (long)((d.L + QW * 4 - 1) / (QW * 4)) * d.N * d.nh;
+        const int dv2_target = ds_wgs <= 128 ? 112 : 224;
+        int slices = (int)((dv2_target + base - 1) / base);
+        const int max_slices = (d.L + 255) / 256;                    // >= 4 q-tiles per slice
+        if (slices > max_slices) slices = max_slices;
+        if (slices < 1) slices = 1;
+        int per = (d.L + slices - 1) / slices;
+        per = ((per + 63) / 64) * 64;
+        slices = (d.L + per - 1) / per;
+        // dS and dV share ONE launch (rcda_bwd_all_kernel) at every shape the two-step dV covers with H <= 64.  (Rounds 2-5 merged only when the dS
+        // grid left most CUs free -- decoder: 48 workgroups --, because at the encoder shape 61 + 33 us became 117 us with the kernels of that time.)
+        // Round 6: with the dS body 13 % shorter and the dV workgroups on two query slices the shared launch wins at the encoder shape too (dS + dV
+        // 82 -> 76.4-77.1 us; 50 x 84 keys, L = 4200: 275 -> 176 us; step -0.02...-0.09 ms in three same-lease pairs, profiles/r6_ab_rcda_slices.txt).
+        if (NF == 1) return launch_rcda_bwd_all<1, 4>(d, st, hgroups, slices, per);
+        if (NF == 2) return wg5 ? launch_rcda_bwd_all<2, 5>(d, st, hgroups, slices, per) : launch_rcda_bwd_all<2, 4>(d, st, hgroups, slices, per);
+        // H > 64: the dS kernel needs more than the 256 registers a 512-thread block leaves a wave -- never merged, the two-step dV is its own launch
+        if ((rc = launch_rcda_bwd<4, 4>(d, st))) return rc;
         const int bytes = dv2_smem().total * 4;
         if (d.precision == 3) {
             if ((rc = set_smem(rcda_dv2_kernel<1>, bytes, "cdetr_rcda_bwd(dV)"))) return rc;
@@ -1808,30 +1718,28 @@ extern "C" int cdetr_rcda_bwd(const cdetr_rcda_bwd_desc* dp, void* stream) {
         }
         return cdetr_launch_status("cdetr_rcda_bwd(dV)");
     }
-    {   // dV kernel
-        const int bytes = (64 * 32 * NF + 64 * Wp + 64 * 32) * 4;
-        const int wgroups = (d.W + 3) / 4;
-        long base = (long)wgroups * d.N * d.nh;
-        int slices = (int)((1024 + base - 1) / base);
-        const int max_slices = (d.L + 127) / 128;
-        if (slices > max_slices) slices = max_slices;
-        if (slices < 1) slices = 1;
-        int per = (d.L + slices - 1) / slices;
-        per = ((per + 63) / 64) * 64;
-        slices = (d.L + per - 1) / per;
-        dim3 grid(wgroups, d.N * d.nh, slices), block(256);
-        auto dv = [&](auto kern) {
-            if ((rc = set_smem(kern, bytes, "cdetr_rcda_bwd(dV)"))) return;
-            hipLaunchKernelGGL(kern, grid, block, bytes, st, d, per);
-        };
-        rc = CDETR_OK;
-        if (d.precision >= 1) {
-            if (NF == 1) dv(rcda_dv_kernel<1, 1>); else if (NF == 2) dv(rcda_dv_kernel<2, 1>); else dv(rcda_dv_kernel<4, 1>);
-        } else {
-            if (NF == 1) dv(rcda_dv_kernel<1, 0>); else if (NF == 2) dv(rcda_dv_kernel<2, 0>); else dv(rcda_dv_kernel<4, 0>);
-        }
-        if (rc) return rc;
-        if ((rc = cdetr_launch_status("cdetr_rcda_bwd(dV)"))) return rc;
-    }
-    return CDETR_OK;
+    // fp32 mode: dS, then the dV kernel
+    if (NF == 1) rc = launch_rcda_bwd<1, 4>(d, st);
+    else if (NF == 2) rc = wg5 ? launch_rcda_bwd<2, 5>(d, st) : launch_rcda_bwd<2, 4>(d, st);
+    else rc = launch_rcda_bwd<4, 4>(d, st);
+    if (rc) return rc;
+    const int bytes = (64 * 32 * NF + 64 * Wp + 64 * 32) * 4;
+    const int wgroups = (d.W + 3) / 4;
+    const long base = (long)wgroups * d.N * d.nh;
+    int slices = (int)((1024 + base - 1) / base);
+    const int max_slices = (d.L + 127) / 128;
+    if (slices > max_slices) slices = max_slices;
+    if (slices < 1) slices = 1;
+    int per = (d.L + slices - 1) / slices;
+    per = ((per + 63) / 64) * 64;
+    slices = (d.L + per - 1) / per;
+    dim3 grid(wgroups, d.N * d.nh, slices), block(256);
+    auto dv = [&](auto kern) -> int {
+        if ((rc = set_smem(kern, bytes, "cdetr_rcda_bwd(dV)"))) return rc;
+        hipLaunchKernelGGL(kern, grid, block, bytes, st, d, per);
+        return cdetr_launch_status("cdetr_rcda_bwd(dV)");
+    };
+    if (NF == 1) return dv(rcda_dv_kernel<1, 0>);
+    if (NF == 2) return dv(rcda_dv_kernel<2, 0>);
+    return dv(rcda_dv_kernel<4, 0>);
 }

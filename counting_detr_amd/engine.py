@@ -930,15 +930,14 @@ class Trainer:
     def _prefetch_ok(self):
         """The next batch's frozen stage may run beside this step only if (a) a side stream really runs beside the main one (probed), and
         (b) the backward of this step reads layer1's output through its bf16 TWIN only -- the prefetch overwrites the fp32 tensor while the
-        backward is still running, and the weight gradients of layer2[0] (conv1, downsample) read X = that tensor: with CDETR_WGRAD_TWINS=0
-        (or a backward arithmetic that does not feed on twins) they would read it as fp32."""
+        backward is still running, and the weight gradients of layer2[0] (conv1, downsample) read X = that tensor: with a backward arithmetic
+        that does not feed on twins they would read it as fp32."""
         from . import ops
         if not (self._prefetch_on and self.flat_g.is_cuda):
             return False
         self._side_streams()                # (probe: sets self._serial)
         body = self.model.backbone.body
-        return (not self._serial and body.frozen_stage_is_frozen() and ops.bf16_twins()
-                and os.environ.get("CDETR_WGRAD_TWINS", "1") != "0")
+        return (not self._serial and body.frozen_stage_is_frozen() and ops.bf16_twins())
 
     def _frozen_for(self, shape):
         """Static buffers + captured graph of the frozen stage for one padded image shape."""

@@ -1084,8 +1084,7 @@ def conv_dgrad(dz, weight, scale, in_hw, stride=1, pad=0, dil=1, gate=None, resi
     # (the consumers must be twin-fed too: the direct-to-LDS data gradient and the tile-class weight gradient -- more than 1024 rows,
     # 8-channel granularity: csrc/igemm.hip wgrad_has_twins / wgrad_is_direct; a few-row problem keeps its fp32 gradient)
     no_fp32 = (twin_only and twin and TWIN_ONLY and out is None and m is not None and m[3] is not None and dz16 is not None
-               and bwd_precision() == 3 and Cout % 64 == 0 and Cin % 64 == 0 and Nb * Hin * Win > 1024
-               and os.environ.get("CDETR_WGRAD_TWINS", "1") != "0")
+               and bwd_precision() == 3 and Cout % 64 == 0 and Cin % 64 == 0 and Nb * Hin * Win > 1024)
     assert dz is not None or (m is not None and dz16 is not None), "a gradient that exists as a twin only needs the weight images"
     dx = out if out is not None else (None if no_fp32 else torch.empty((Nb, Hin, Win, Cin), device=dz16.device if dz is None else dz.device, dtype=torch.float32))
     dx16 = torch.empty((Nb, Hin, Win, Cin), device=(dz16 if dz is None else dz).device, dtype=torch.bfloat16) if twin else None
@@ -1107,8 +1106,8 @@ def conv_wgrad_(dz, x, weight, scale, stride=1, pad=0, dil=1, dz16=None, x16=Non
     g, Ho2, Wo2 = conv_geom_fwd(H, W, kh, kw, stride, pad, dil)
     assert (Ho2, Wo2) == (Ho, Wo)
     if isinstance(x, Groups):      # no fp32 tensor: only the twin-fed tile kernel can run it (csrc/igemm.hip wgrad_has_twins / wgrad_is_direct)
-        assert x16 is not None and dz16 is not None and bwd_precision() == 3 and Cout % 8 == 0 and Cin % 8 == 0 and Nb * Ho * Wo > 1024 \
-            and os.environ.get("CDETR_WGRAD_TWINS", "1") != "0", "a grouped activation feeds a weight gradient through its bf16 twin"
+        assert x16 is not None and dz16 is not None and bwd_precision() == 3 and Cout % 8 == 0 and Cin % 8 == 0 and Nb * Ho * Wo > 1024, \
+            "a grouped activation feeds a weight gradient through its bf16 twin"
         x = None                   # cdetr_wgrad_desc.X == NULL: the C side refuses any kernel class but the twin-fed one
     gw = grad_buffer(weight)
     assert gw.is_contiguous(memory_format=torch.channels_last) or (kh == 1 and kw == 1)

@@ -169,7 +169,7 @@ typedef struct {
                        /* dY and / or X may be NULL when the tensor exists as its twin only (an inner gradient written with cdetr_gemm_desc.C  */
                        /* == NULL; an activation kept as interleaved groups + twin): the twin-fed tile kernel must then be the one that runs   */
                        /* (more than 1024 pixels, the conditions above), CDETR_ERR_ARG otherwise -- never a silent read of a missing tensor.   */
-                       /* CDETR_WGRAD_KP (environment, A/B): 32-pixel blocks staged per barrier by the twin-fed kernels, 1 (default) / 2 / 4.  */
+                       /* CDETR_WGRAD_KP (environment, under CDETR_TUNING): 32-pixel blocks staged per barrier by the twin-fed kernels, 1 (default) / 2 / 4. */
 } cdetr_wgrad_desc;
 int cdetr_wgrad(const cdetr_wgrad_desc* d, void* stream);
 /* n INDEPENDENT weight-gradient problems submitted together (same semantics as n cdetr_wgrad calls in any order; problems may

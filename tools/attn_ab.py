@@ -1,9 +1,8 @@
 """Kernel times of cdetr_attn_fwd / cdetr_attn_bwd at the nn.MultiheadAttention variant's sizes (N=2, nh=8) -> one JSON line.
 
-    CDETR_ATTN_KEY_SPLIT=0|1 CDETR_ATTN_BWD_TWO_LAUNCHES=0|1 python tools/attn_ab.py
+    CDETR_ATTN_BWD_TWO_LAUNCHES=0|1 python tools/attn_ab.py
 
-The two switches are read once per process (csrc/mha.hip): run once per setting to compare the forward's key split and the backward's
-one launch against two.  Times are medians over 50 launches between events, after 5 warm-up launches.
+The switch is read once per process (csrc/mha.hip): run once per setting to compare the backward's one launch against two.  Times are medians over 50 launches between events, after 5 warm-up launches.
 """
 import json
 import os
@@ -34,7 +33,7 @@ def main():
     from counting_detr_amd import ops
     N, nh, E = 2, 8, 256
     g = torch.Generator().manual_seed(0)
-    res = {"key_split": os.environ.get("CDETR_ATTN_KEY_SPLIT", "rule"), "bwd_two_launches": os.environ.get("CDETR_ATTN_BWD_TWO_LAUNCHES", "0")}
+    res = {"bwd_two_launches": os.environ.get("CDETR_ATTN_BWD_TWO_LAUNCHES", "0")}
     for Lq, Lk in SHAPES:
         q = torch.randn(N, Lq, E, generator=g).cuda().requires_grad_(True)
         k = torch.randn(N, Lk, E, generator=g).cuda().requires_grad_(True)

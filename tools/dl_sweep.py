@@ -5,6 +5,7 @@ direct-to-LDS kernel the pre-split planes.  Both write C (fp32) + C16 (+ C16lo f
 usage: python tools/dl_sweep.py [fwd|bwd|all] [M-multiplier]"""
 import os
 import sys
+os.environ.setdefault("CDETR_TUNING", "1")      # CDETR_GEMM_DL is only consulted when this is set at load time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from counting_detr_amd import ops, _ffi
@@ -94,7 +95,7 @@ def run(shape, precision, mult=1):
 
 
 if __name__ == "__main__":
-    os.environ["CDETR_GEMM_DL"] = "0"          # cdetr_gemm itself stays on the register-staged kernels (read once at first call)
+    os.environ["CDETR_GEMM_DL"] = "0"          # cdetr_gemm itself stays on the register-staged kernels (read per call)
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     mult = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     names = {0: "128x128", 1: "128x64", 2: "64x128", 3: "64x64"}

@@ -5,6 +5,7 @@ with 5-wave and 4-wave workgroups, decoder shape (300 queries).  usage: python t
 import os
 import subprocess
 import sys
+os.environ.setdefault("CDETR_TUNING", "1")      # CDETR_RCDA_PROBE is read per call, under CDETR_TUNING only
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
@@ -62,7 +63,7 @@ def child_bwd(nw):
         g = torch.Generator(device=dev).manual_seed(1)
         mk = lambda *s: torch.randn(*s, device=dev, generator=g)
         q_row, q_col, k_row, k_col, v, dO = mk(N, L, E), mk(N, L, E), mk(N, W, E), mk(N, H, E), mk(N, H, W, E), mk(N, L, E)
-        os.environ.pop("CDETR_RCDA_PROBE", None)      # (the forward below is the product kernel; its static was read at the first call anyway)
+        os.environ.pop("CDETR_RCDA_PROBE", None)      # (the forward below is the product kernel)
         o, a_row, a_col = ops.rcda_fwd_raw(q_row, q_col, k_row, k_col, v, None, None, nh, save=True)
         Hp, Wp = ops.rcda_pads(H, W)
         nwg = ((L + 32 * nw - 1) // (32 * nw)) * N * nh
@@ -79,7 +80,7 @@ def child_bwd(nw):
         d.k_row, d.k_col, d.dq_row, d.dq_col = ptr(k_row), ptr(k_col), ptr(dq_row), ptr(dq_col)
         d.q_row, d.q_col, d.dk_row, d.dk_col = ptr(q_row), ptr(q_col), ptr(dk_row), ptr(dk_col)
         d.ds_row, d.ds_col = ptr(stamps), ptr(dummy)
-        os.environ["CDETR_RCDA_PROBE"] = str(nw)      # read once, at the first cdetr_rcda_bwd call
+        os.environ["CDETR_RCDA_PROBE"] = str(nw)      # read at every cdetr_rcda_bwd call
         evs = []
         for _ in range(4):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -104,14 +105,10 @@ if __name__ == "__main__":
     elif os.environ.get("CDETR_RCDA_PROBE"):
         child(int(os.environ["CDETR_RCDA_PROBE"]))
     else:
-        for rg in (1, 2):
-            print(f"== key rows per barrier (CDETR_RCDA_RG) = {rg}", flush=True)
-            for nw in (5, 4):
-                subprocess.check_call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, CDETR_RCDA_PROBE=str(nw), CDETR_RCDA_RG=str(rg)))
+        for nw in (5, 4):
+            subprocess.check_call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, CDETR_RCDA_PROBE=str(nw)))
         print("== backward: dS / dq / dk kernel", flush=True)
         for nw in (5, 4):
             subprocess.check_call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, CDETR_RCDA_PROBE=str(nw), RCDA_PROBE_BWD="1"))
         print("== un-instrumented kernels, HIP events (tools/rcda_time.py)", flush=True)
-        for rg in (1, 2):
-            print(f"CDETR_RCDA_RG={rg}", flush=True)
-            subprocess.check_call([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "rcda_time.py")], env=dict(os.environ, CDETR_RCDA_RG=str(rg)))
+        subprocess.check_call([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "rcda_time.py")])

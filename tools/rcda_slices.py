@@ -1,5 +1,5 @@
 """Key-row slices of the two-step RCDA forward (cdetr_rcda_fwd_desc.ws): HIP-event time per launch at the encoder (L = H*W) and decoder
-(L = 300) shapes for every slice count and both workgroup widths.  CDETR_TUNING=1 is needed (the knobs are re-read per call)."""
+(L = 300) shapes for every slice count.  CDETR_TUNING=1 is needed (CDETR_RCDA_HS is re-read per call)."""
 import os, sys
 os.environ["CDETR_TUNING"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,16 +35,10 @@ for (H, W) in ((50, 50), (24, 36)):
         k_row, k_col = torch.randn(N, W, E, device=dev), torch.randn(N, H, E, device=dev)
         v = torch.randn(N, H, W, E, device=dev)
         row = []
-        for nw in (4, 2):
-            os.environ["CDETR_RCDA_NW"] = str(nw)
-            for nw5 in ((1, 0) if nw == 4 else (0,)):
-                os.environ["CDETR_RCDA_NW5"] = str(nw5)
-                for hs in (1, 2, 3, 4, 6):
-                    os.environ["CDETR_RCDA_HS"] = str(hs)
-                    t = timeit(lambda: ops.rcda_fwd_raw(q_row, q_col, k_row, k_col, v, None, None, nh))
-                    row.append("nw%d%s/hs%d %5.1f" % (nw, "+5" if nw5 else "", hs, t))
+        for hs in (1, 2, 3, 4, 6):
+            os.environ["CDETR_RCDA_HS"] = str(hs)
+            t = timeit(lambda: ops.rcda_fwd_raw(q_row, q_col, k_row, k_col, v, None, None, nh))
+            row.append("hs%d %5.1f" % (hs, t))
         os.environ.pop("CDETR_RCDA_HS")
-        os.environ.pop("CDETR_RCDA_NW")
-        os.environ.pop("CDETR_RCDA_NW5", None)
         t = timeit(lambda: ops.rcda_fwd_raw(q_row, q_col, k_row, k_col, v, None, None, nh))
         print("H=%d W=%d L=%d  default %5.1f us | %s" % (H, W, L, t, "  ".join(row)), flush=True)

@@ -1,8 +1,8 @@
 """RCDA core at the FSCD-LVIS map sizes (BASELINE configs[3]: images up to 800 x 1333 -> 50 x 84 keys at stride 16, or 84 x 50 for a
-portrait image) against the square 50 x 50 map of configs[1]: HIP-event time per call and algorithmic TF, with the round-6 wide-map
-kernels (rcda_fwd2_kernel<4, 5|6> / <.., TH = 3>, rcda_dv2 key-column chunks) and with CDETR_RCDA_WIDE=0 (the rounds 1-5 dispatch: W > 64
-falls back to rcda_fwd_kernel / rcda_dv_kernel).  -> profiles/r6_rcda_wide.txt"""
-import os, subprocess, sys
+portrait image) against the square 50 x 50 map of configs[1]: HIP-event time per call and algorithmic TF of the wide-map kernels
+(rcda_fwd2_kernel<4, 5|6> / <.., TH = 3>, rcda_dv2 key-column chunks).  profiles/r6_rcda_wide.txt also holds the rounds 1-5 dispatch
+(W > 64 on rcda_fwd_kernel / rcda_dv_kernel), which is gone."""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
@@ -35,10 +35,4 @@ def child():
 
 
 if __name__ == "__main__":
-    if os.environ.get("RCDA_WIDE_CHILD"):
-        child()
-    else:
-        for wide in ("1", "0"):
-            print("== CDETR_RCDA_WIDE=%s (%s)" % (wide, "round 6 dispatch" if wide == "1" else "rounds 1-5 dispatch: W > 64 on the fallback kernels"), flush=True)
-            env = dict(os.environ, RCDA_WIDE_CHILD="1", CDETR_RCDA_WIDE=wide)
-            subprocess.check_call([sys.executable, os.path.abspath(__file__)], env=env)
+    child()
