@@ -58,6 +58,10 @@ def get_args_parser():
     p.add_argument("--cache_mode", default=False, action="store_true")
     p.add_argument("--ap_on_host", action="store_true",
                    help="infer.py: box AP through coco_ap's interpreted host path instead of the device matcher (same numbers, minutes on crowded splits)")
+    p.add_argument("--device_detections", action="store_true",
+                   help="infer.py / main.py --eval: threshold, scaling, truncation and COCOeval's ordering of the detections on the device "
+                        "(cdetr_emit_detections, one call per image, one copy back per split); the same predictions json byte for byte, the box "
+                        "AP matched from device memory without re-reading it (--ap_on_host: ap_from_json on the written file)")
     # additions of this build (the reference hard-codes batch 1 on one GPU)
     p.add_argument("--dataset", default="fsc147", choices=["fsc147", "fscd_lvis"], help="reader used without --synthetic")
     p.add_argument("--images_per_gpu", default=2, type=int, help="local batch of the data-parallel trainer")

@@ -26,6 +26,10 @@ code below, untouched, and stays the checker): `pack_images` flattens all images
 evaluation order), ONE `cdetr_coco_match` launch (csrc/coco_eval.hip) matches every image under every area range and IoU threshold, the
 flags come back in one copy and `accumulate` forms `precision[T, R]` with array operations -- the same float64 operations in the same
 order as the loops of `average_precision`, so the two paths return EQUAL numbers (tests/test_coco_ap_device_cpu.py, _gpu.py).
+
+STORE PATH (`summarize_store`): the detections never visit the host as dicts -- cdetr_emit_detections (csrc/detections.hip) left them in an
+ops.DetectionStore in evaluation order, `pack_store` packs only the ground truths and `match_on_device` reads the detections from device memory;
+the same launch, the same `accumulate`, EQUAL numbers again (tests/test_detections_gpu.py).
 """
 import json
 
@@ -114,17 +118,21 @@ def pack_images(gt_by_img, dt_by_img, max_det=MAX_DETS):
     for i in ids:
         d = dt_by_img.get(i, [])
         dts.append([d[j] for j in np.argsort([-x["score"] for x in d], kind="mergesort")[:max_det]])
-    flat_g = [g for gl in gts for g in gl]
     flat_d = [d for dl in dts for d in dl]
-    return {"image_ids": ids,
-            "gt_boxes": np.array([g["bbox"] for g in flat_g], dtype=np.float64).reshape(-1, 4),
-            "gt_area": np.array([g["area"] for g in flat_g], dtype=np.float64),
-            "gt_ignore": np.array([bool(g.get("ignore", 0)) or bool(g.get("iscrowd", 0)) for g in flat_g], dtype=np.uint8),
-            "gt_off": np.concatenate([[0], np.cumsum([len(gl) for gl in gts])]).astype(np.int32),
+    return {"image_ids": ids, **_pack_gts(gts),
             "dt_boxes": np.array([d["bbox"] for d in flat_d], dtype=np.float64).reshape(-1, 4),
             "dt_area": np.array([d.get("area", d["bbox"][2] * d["bbox"][3]) for d in flat_d], dtype=np.float64),
             "dt_score": np.array([d["score"] for d in flat_d], dtype=np.float64),
-            "dt_off": np.concatenate([[0], np.cumsum([len(dl) for dl in dts])]).astype(np.int32),
+            "dt_off": np.concatenate([[0], np.cumsum([len(dl) for dl in dts])]).astype(np.int32)}
+
+
+def _pack_gts(gts):
+    """The ground-truth half of `pack_images`: the images' lists, in evaluation order of the images -> gt_boxes, gt_area, gt_ignore, gt_off, g_max."""
+    flat_g = [g for gl in gts for g in gl]
+    return {"gt_boxes": np.array([g["bbox"] for g in flat_g], dtype=np.float64).reshape(-1, 4),
+            "gt_area": np.array([g["area"] for g in flat_g], dtype=np.float64),
+            "gt_ignore": np.array([bool(g.get("ignore", 0)) or bool(g.get("iscrowd", 0)) for g in flat_g], dtype=np.uint8),
+            "gt_off": np.concatenate([[0], np.cumsum([len(gl) for gl in gts])]).astype(np.int32),
             "g_max": max([len(gl) for gl in gts], default=0)}
 
 
@@ -164,24 +172,29 @@ def _cuda(device):
 def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None):
     """One `cdetr_coco_match` launch for every image of `pack` (from `pack_images`) under the area ranges `areas` ->
     (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int): `_evaluate_image`'s flags, images side by side.
-    `events`: a pair of torch.cuda.Event recorded around the launch."""
+    `events`: a pair of torch.cuda.Event recorded around the launch.  A pack that carries "dt_device" = (boxes f64 [D, 4], area f64 [D]) device
+    tensors (`summarize_store`) has its detections read from there; its dt_boxes / dt_area are not used."""
     import torch
     from . import ops
     device = _cuda(device)
     A, T, B, D = len(areas), len(IOU_THRS), len(pack["image_ids"]), len(pack["dt_score"])
+    dt_dev = pack.get("dt_device")
     if B == 0:
         return np.zeros((A, T, 0), dtype=bool), np.zeros((A, T, 0), dtype=bool), np.zeros((A, 0), dtype=np.int64)
     thrs = np.minimum(IOU_THRS, 1 - 1e-10)
     rng = np.array([AREA_RNG[a] for a in areas], dtype=np.float64).reshape(-1)
     G = len(pack["gt_area"])
-    f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], pack["dt_boxes"].reshape(-1), pack["dt_area"], thrs, rng])
+    dt_host = (pack["dt_boxes"].reshape(-1), pack["dt_area"]) if dt_dev is None else (np.zeros(0), np.zeros(0))
+    f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], dt_host[0], dt_host[1], thrs, rng])
     i32 = np.concatenate([pack["gt_off"], pack["dt_off"]]).astype(np.int32)
     with torch.cuda.device(device):
         f = torch.from_numpy(f64).to(device)
         i = torch.from_numpy(i32).to(device)
         ig = torch.from_numpy(pack["gt_ignore"]).to(device)
-        cuts = np.cumsum([0, 4 * G, G, 4 * D, D, T, 2 * A])
+        cuts = np.cumsum([0, 4 * G, G, len(dt_host[0]), len(dt_host[1]), T, 2 * A])
         gt_boxes, gt_area, dt_boxes, dt_area, d_thrs, d_rng = (f[cuts[k]:cuts[k + 1]] for k in range(6))
+        if dt_dev is not None:
+            dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
         matched, ignored, npig = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]),
                                                 host=True, events=events)
     return matched, ignored, npig
@@ -240,18 +253,78 @@ def _mean(p):
     return float(np.mean(p)) if p.size else -1.0
 
 
+def _six(by_area):
+    """precision[T, R] per area range -> the six reported numbers (x 100, NaN when undefined)."""
+    p_all = by_area["all"]
+    vals = {"AP": _mean(p_all), "AP50": _mean(p_all[np.isclose(IOU_THRS, 0.5)]), "AP75": _mean(p_all[np.isclose(IOU_THRS, 0.75)]),
+            "APs": _mean(by_area["small"]), "APm": _mean(by_area["medium"]), "APl": _mean(by_area["large"])}
+    return {k: (v * 100 if v >= 0 else float("nan")) for k, v in vals.items()}
+
+
 def summarize(gt_by_img, dt_by_img, max_det=MAX_DETS, device=None):
     """The six numbers of A2/eval_all.py:331 (x 100, NaN when undefined): AP, AP50, AP75, APs, APm, APl.
     `device`: a CUDA device = all four area ranges matched in one launch, the same six numbers."""
     if device is not None:
         by_area = dict(zip(AREA_RNG, _device_precisions(gt_by_img, dt_by_img, tuple(AREA_RNG), max_det, device)))
     else:
-        by_area = None
-    p_all = by_area["all"] if by_area else average_precision(gt_by_img, dt_by_img, "all", max_det)
-    vals = {"AP": _mean(p_all), "AP50": _mean(p_all[np.isclose(IOU_THRS, 0.5)]), "AP75": _mean(p_all[np.isclose(IOU_THRS, 0.75)])}
-    for key, area in (("APs", "small"), ("APm", "medium"), ("APl", "large")):
-        vals[key] = _mean(by_area[area] if by_area else average_precision(gt_by_img, dt_by_img, area, max_det))
-    return {k: (v * 100 if v >= 0 else float("nan")) for k, v in vals.items()}
+        by_area = {area: average_precision(gt_by_img, dt_by_img, area, max_det) for area in AREA_RNG}
+    return _six(by_area)
+
+
+def pack_store(gt_by_img, store, image_ids):
+    """`pack_images` for detections that are already on the device in evaluation order (an ops.DetectionStore; image k of the store is
+    `image_ids[k]`): the ground truths are packed on the host, the detections stay where they are.  Images in sorted-id order, those with neither
+    ground truth nor detection left out, exactly as `pack_images` orders them; when that is not the store's own order the segments are
+    gathered on the device with an index built from the store's offsets.  -> the pack of `match_on_device` with "dt_device" (and dt_score, dt_off
+    on the host; no dt_boxes / dt_area)."""
+    import torch
+    host = store.finish()                                                  # the one copy (cached by the store)
+    image_ids = [int(i) for i in image_ids]
+    if len(image_ids) != store.first or len(set(image_ids)) != len(image_ids):
+        raise RuntimeError(f"coco_ap: {len(image_ids)} image ids ({len(set(image_ids))} distinct) for a store of {store.first} images")
+    off = host["eval_off"].astype(np.int64)
+    slot = {i: k for k, i in enumerate(image_ids)}
+    n_dt = lambda i: int(off[slot[i] + 1] - off[slot[i]]) if i in slot else 0                                  # noqa: E731
+    ids = [i for i in sorted(set(gt_by_img) | set(image_ids)) if gt_by_img.get(i) or n_dt(i)]
+    segs = [(int(off[slot[i]]), int(off[slot[i] + 1])) for i in ids if i in slot and n_dt(i)]
+    E = int(off[store.first])
+    in_place = sum(hi - lo for lo, hi in segs) == E and all(a[1] == b[0] for a, b in zip(segs, segs[1:])) and (not segs or segs[0][0] == 0)
+    boxes, area, score = store.eval_boxes[:E], store.eval_area[:E], host["eval_score"]
+    if not in_place:
+        idx = np.concatenate([np.arange(lo, hi) for lo, hi in segs]) if segs else np.zeros(0, dtype=np.int64)
+        di = torch.from_numpy(idx).to(store.buf.device)
+        boxes, area = boxes.index_select(0, di), area.index_select(0, di)
+        score = score[idx]
+    return {"image_ids": ids, **_pack_gts([gt_by_img.get(i, []) for i in ids]), "dt_device": (boxes.contiguous(), area.contiguous()),
+            "dt_score": np.ascontiguousarray(score), "dt_off": np.concatenate([[0], np.cumsum([n_dt(i) for i in ids])]).astype(np.int32)}
+
+
+def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS):
+    """`summarize(..., device=)` for an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections): the same six numbers
+    as `ap_from_json(device=)` gives on the predictions json written from that store, without the json trip -- the evaluation records go to
+    cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image k; `gt_by_img` as for `summarize`
+    (`gt_from_json`).  `device`: the store's own (default)."""
+    if store.max_det != max_det:
+        raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
+    device = store.buf.device if device is None else _cuda(device)
+    pack = pack_store(gt_by_img, store, image_ids)
+    areas = tuple(AREA_RNG)
+    matched, ignored, npig = match_on_device(pack, device, areas)
+    by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(areas)}
+    return _six(by_area)
+
+
+def gt_from_json(gt_json, ids):
+    """{image_id: [ground truth dicts]} of `instances_<split>.json` for the images `ids`, as `ap_from_json` forms them."""
+    with open(gt_json) as f:
+        gt = json.load(f)
+    ids, gt_by = set(ids), {}
+    for a in gt.get("annotations", []):
+        if a["image_id"] in ids:
+            b = [float(v) for v in a["bbox"]]
+            gt_by.setdefault(a["image_id"], []).append({"bbox": b, "area": float(a.get("area", b[2] * b[3])), "iscrowd": a.get("iscrowd", 0),
+                                                        "ignore": a.get("ignore", 0)})
+    return gt_by
 
 
 def ap_from_json(pred_json, gt_json, image_ids=None, device=None):
@@ -259,15 +332,8 @@ def ap_from_json(pred_json, gt_json, image_ids=None, device=None):
     `device`: passed to `summarize`."""
     with open(pred_json) as f:
         pred = json.load(f)
-    with open(gt_json) as f:
-        gt = json.load(f)
     ids = set(image_ids) if image_ids is not None else {im["id"] for im in pred.get("images", [])} or {a["image_id"] for a in pred["annotations"]}
-    gt_by, dt_by = {}, {}
-    for a in gt.get("annotations", []):
-        if a["image_id"] in ids:
-            b = [float(v) for v in a["bbox"]]
-            gt_by.setdefault(a["image_id"], []).append({"bbox": b, "area": float(a.get("area", b[2] * b[3])), "iscrowd": a.get("iscrowd", 0),
-                                                        "ignore": a.get("ignore", 0)})
+    gt_by, dt_by = gt_from_json(gt_json, ids), {}
     for a in pred.get("annotations", []):
         if a["image_id"] in ids:
             b = reference_box(a["bbox"])

@@ -2039,6 +2039,91 @@ def image_prep(raw, events=None):
     return image, mask
 
 
+def emit_detections(prob, boxes, points, orig_hw, store, first, events=None):
+    """cdetr_emit_detections: append the detections of one forwarded batch to `store` (a DetectionStore) as its images first .. first + B - 1.
+    Device tensors: prob fp32 [B, Q] (the counting rule's own sigmoid), boxes fp32 [B, Q, 4] normalised cxcywh, points fp32 [B, Q, 2], orig_hw
+    int32 [B, 2] = (height, width).  One call on the current stream, nothing comes back to the host; a record range that does not fit the
+    store sets its status word (DetectionStore.finish raises).  events: a pair of torch.cuda.Event recorded right before / after the call."""
+    from ._ffi import EmitDetectionsDesc
+    for name, t, dt_ in (("prob", prob, torch.float32), ("boxes", boxes, torch.float32), ("points", points, torch.float32), ("orig_hw", orig_hw, torch.int32)):
+        if t.dtype != dt_ or not t.is_contiguous():
+            raise RuntimeError(f"emit_detections: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    if prob.dim() != 2 or tuple(boxes.shape) != tuple(prob.shape) + (4,) or tuple(points.shape) != tuple(prob.shape) + (2,) \
+            or tuple(orig_hw.shape) != (prob.shape[0], 2):
+        raise RuntimeError(f"emit_detections: prob [B, Q], boxes [B, Q, 4], points [B, Q, 2], orig_hw [B, 2] expected, got {tuple(prob.shape)}, "
+                           f"{tuple(boxes.shape)}, {tuple(points.shape)}, {tuple(orig_hw.shape)}")
+    B, Q = prob.shape
+    if Q != store.Q or prob.device != store.buf.device:
+        raise RuntimeError(f"emit_detections: Q = {Q} on {prob.device} into a store of Q = {store.Q} on {store.buf.device}")
+    d = EmitDetectionsDesc()
+    d.B, d.Q, d.N, d.first, d.max_det, d.wire_cap, d.eval_cap = B, Q, store.N, int(first), store.max_det, store.wire_cap, store.eval_cap
+    d.threshold = store.threshold
+    d.prob, d.boxes, d.points, d.orig_hw = ptr(prob), ptr(boxes), ptr(points), ptr(orig_hw)
+    d.counts, d.wire_off, d.eval_off, d.status = ptr(store.counts), ptr(store.wire_off), ptr(store.eval_off), ptr(store.status)
+    d.wire, d.eval_boxes, d.eval_area, d.eval_score = ptr(store.wire), ptr(store.eval_boxes), ptr(store.eval_area), ptr(store.eval_score)
+    if events is not None:
+        events[0].record()
+    check(lib().cdetr_emit_detections(C.byref(d), stream_ptr()), "cdetr_emit_detections")
+    if events is not None:
+        events[1].record()
+
+
+class DetectionStore:
+    """The detections of a whole split on the device, filled batch by batch by cdetr_emit_detections (`emit`) and read back ONCE (`finish`).
+    One byte buffer: [status | counts [N] | wire_off [N + 1] | eval_off [N + 1] | eval_score f64 [eval_cap] | wire int32 [wire_cap, 8]] is what
+    `finish` copies; [eval_boxes f64 [eval_cap, 4] | eval_area f64 [eval_cap]] behind it never leaves the device (coco_ap.summarize_store hands
+    them to cdetr_coco_match).  Capacities default to the worst case, N * Q wire and N * min(Q, max_det) evaluation records."""
+
+    def __init__(self, n_images, n_queries, device, threshold=0.5, max_det=1100, wire_cap=None, eval_cap=None):
+        self.N, self.Q, self.threshold, self.max_det = int(n_images), int(n_queries), float(threshold), int(max_det)
+        if self.N < 1 or self.Q < 1 or self.max_det < 0:
+            raise RuntimeError(f"DetectionStore: bad sizes N = {self.N}, Q = {self.Q}, max_det = {self.max_det}")
+        self.wire_cap = self.N * self.Q if wire_cap is None else int(wire_cap)
+        self.eval_cap = self.N * min(self.Q, self.max_det) if eval_cap is None else int(eval_cap)
+        if max(self.wire_cap, self.eval_cap) > 1 << 30:
+            raise RuntimeError(f"DetectionStore: {self.wire_cap} / {self.eval_cap} records exceed the 2^30 of cdetr_emit_detections")
+        al = lambda n: (n + 15) // 16 * 16                                                                     # noqa: E731
+        N, cuts = self.N, [0]
+        for nbytes in (16, 4 * N, 4 * (N + 1), 4 * (N + 1), 8 * self.eval_cap, 32 * self.wire_cap, 32 * self.eval_cap, 8 * self.eval_cap):
+            cuts.append(cuts[-1] + al(nbytes))
+        self.buf = torch.empty(cuts[-1], dtype=torch.uint8, device=device)
+        self.buf[:cuts[4]].zero_()                                                                             # status, counts, wire_off[0], eval_off[0]
+        part = lambda k, dt_, n: self.buf[cuts[k]:cuts[k + 1]].view(dt_)[:n]                                   # noqa: E731
+        self.status, self.counts = part(0, torch.int32, 1), part(1, torch.int32, N)
+        self.wire_off, self.eval_off = part(2, torch.int32, N + 1), part(3, torch.int32, N + 1)
+        self.eval_score, self.wire = part(4, torch.float64, self.eval_cap), part(5, torch.int32, 8 * self.wire_cap).view(-1, 8)
+        self.eval_boxes, self.eval_area = part(6, torch.float64, 4 * self.eval_cap).view(-1, 4), part(7, torch.float64, self.eval_cap)
+        self._cuts, self.first, self._host = cuts, 0, None
+
+    def emit(self, prob, boxes, points, orig_hw, events=None):
+        """Append one forwarded batch (see emit_detections); returns the store index of its first image."""
+        first, B = self.first, prob.shape[0]
+        if first + B > self.N:
+            raise RuntimeError(f"DetectionStore: image {first + B} into a store of {self.N}")
+        emit_detections(prob, boxes, points, orig_hw, self, first, events=events)
+        self.first, self._host = first + B, None
+        return first
+
+    def finish(self):
+        """ONE device -> host copy (it waits for the emits): dict of numpy arrays for the n images emitted so far -- counts [n], wire_off /
+        eval_off [n + 1], wire int32 [W, 7] (cx, cy, w, h, area, px, py), score fp32 [W], eval_score f64 [E].  Raises if a record range did
+        not fit the store."""
+        if self._host is None:
+            c, n = self._cuts, self.first
+            h = self.buf[:c[6]].cpu().numpy()
+            status = int(h[:4].view("int32")[0])
+            if status:
+                raise RuntimeError(f"DetectionStore: cdetr_emit_detections reported status {status} (1: more than {self.wire_cap} wire records, "
+                                   f"2: more than {self.eval_cap} evaluation records, 4: inconsistent offsets); the images concerned were not written")
+            i32 = lambda k, m: h[c[k]:c[k] + 4 * m].view("int32")                                              # noqa: E731
+            wire_off, eval_off = i32(2, n + 1), i32(3, n + 1)
+            W, E = int(wire_off[n]), int(eval_off[n])
+            rec = h[c[5]:c[5] + 32 * W].view("int32").reshape(W, 8)
+            self._host = {"counts": i32(1, n), "wire_off": wire_off, "eval_off": eval_off, "wire": rec[:, :7], "score": rec[:, 7].view("float32"),
+                          "eval_score": h[c[4]:c[4] + 8 * E].view("float64")}
+        return self._host
+
+
 class CriterionFn(torch.autograd.Function):
     """SetCriterion's six scalars in one launch (cdetr_criterion_fwd); returns (vec, total) with
     vec = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou, loss_variance] and total = sum_k w6[k] vec[k] (the weighted

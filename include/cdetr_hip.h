@@ -537,6 +537,51 @@ typedef struct {
 } cdetr_image_prep_desc;
 int cdetr_image_prep(const cdetr_image_prep_desc* d, void* stream);
 
+/* ---- detections emitted on the device (csrc/detections.hip): what the reference's inference driver does per image on the host between
+ * the forward and the evaluator -- threshold, scaling to original pixels, int() of every field (A2/infer.py:75-116) -- plus the evaluator's
+ * box conversion (A2/eval_all.py:165-169) and COCOeval's detection order (descending score, stable, cut at maxDets), EQUAL to that host path
+ * (infer.py's loop, coco_ap.reference_box, coco_ap.pack_images); FMA contraction is switched off in this translation unit.
+ * cdetr_emit_detections: ONE call per forwarded batch (a count kernel and an emit kernel, one workgroup per image, on `stream`), appending
+ *   the batch's images first .. first + B - 1 to a device-resident STORE that holds a whole split of N images:
+ *     counts [N]       kept queries per image (prob >= threshold; a NaN probability is dropped);
+ *     wire_off [N + 1] / eval_off [N + 1]: image n owns wire records wire_off[n] .. wire_off[n + 1] and evaluation records
+ *                      eval_off[n] .. eval_off[n + 1].  The call READS entry `first` (written by the previous call in stream order; entry 0 is
+ *                      zeroed by the caller once) and writes entries first + 1 .. first + B as running sums of this batch's own counts.
+ *                      Placement is deterministic: no atomic decides where or in what order a record lands.
+ *     wire [wire_cap][8] int32, QUERY order: with W = (float)ori_w, H = (float)ori_h and fx = box0 * W, fy = box1 * H, fw = box2 * W,
+ *                      fh = box3 * H (one fp32 multiply each): { trunc(fx), trunc(fy), trunc(fw), trunc(fh), trunc(fw * fh) (fp32 product of
+ *                      the unrounded fw, fh), trunc(px * W), trunc(py * H), the bits of the fp32 score } -- the bbox, area, point and score of a
+ *                      predictions json annotation.  Truncation toward zero.
+ *     eval_boxes [eval_cap][4], eval_area, eval_score [eval_cap] float64, EVALUATION order (descending score, equal scores in ascending
+ *                      query order, at most max_det per image): with cx, cy, w, h the truncated wire integers,
+ *                      box = { tdiv2(2 cx - w), tdiv2(2 cy - h), w, h } (integer division by 2 truncating toward zero = int(cx - w / 2); negative
+ *                      for a box that overhangs the left / top edge), area = w * h, score = the fp32 score widened -- cdetr_coco_match's
+ *                      dt_boxes / dt_area and the scores of the accumulation, image after image.
+ *   Every range is checked against wire_cap / eval_cap (records) before anything is addressed: an image that does not fit writes NOTHING and
+ *   ORs a bit into *status (1: wire records, 2: evaluation records, 4: the offsets at `first` do not describe this store); the offsets keep
+ *   running.  The caller zeroes *status once and raises when it reads the store back.  Limits: Q <= 4096 (the keys of an image are sorted in
+ *   LDS), B <= 65535, CDETR_ERR_UNSUPPORTED beyond; first + B <= N; capacities <= 2^30 records; wire 16-byte aligned.                       */
+typedef struct {
+    int32_t B, Q;               /* images in this batch, queries per image */
+    int32_t N, first;           /* images the store holds; store index of this batch's first image */
+    int32_t max_det;            /* cut of the evaluation records per image (COCOeval's maxDets[-1], 1100 in the reference) */
+    int32_t wire_cap, eval_cap; /* capacities in records (worst case: N * Q and N * min(Q, max_det)) */
+    float threshold;            /* a query is kept when prob >= threshold */
+    const float* prob;          /* [B][Q] sigmoid(logit[..., 0]) as the counting rule formed it */
+    const float* boxes;         /* [B][Q][4] normalised cxcywh */
+    const float* points;        /* [B][Q][2] normalised reference points (x, y) */
+    const int32_t* orig_hw;     /* [B][2] original (height, width) in pixels */
+    int32_t* counts;            /* [N] */
+    int32_t* wire_off;          /* [N + 1] */
+    int32_t* eval_off;          /* [N + 1] */
+    int32_t* wire;              /* [wire_cap][8] */
+    double* eval_boxes;         /* [eval_cap][4] xywh */
+    double* eval_area;          /* [eval_cap] */
+    double* eval_score;         /* [eval_cap] */
+    int32_t* status;            /* [1] overflow bits, zeroed by the caller once */
+} cdetr_emit_detections_desc;
+int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream);
+
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);
 /* Stream plumbing of the trainer (no reference counterpart: the reference runs one stream and drains it every step, A2/engine.py:33-57).

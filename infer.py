@@ -9,7 +9,13 @@ AP50 / AP75 / APs / APm / APl of A2/eval_all.py:285-331 from a dependency-free r
 (counting_detr_amd/coco_ap.py; parity unpinned: there is no pycocotools in this image to check it against).  On a CUDA device the AP's
 matching runs there (one cdetr_coco_match launch for the split); `--ap_on_host` keeps the interpreted host path, which gives the same numbers.
 
+`--device_detections` (off by default; the host loop stays the checker): the detections leave the forward in the form the matcher reads.  One
+cdetr_emit_detections call per image appends its wire records (the json's fields) and its evaluation records (reference_box + COCOeval's order) to
+a device-resident store, the losses go to a device buffer, and nothing is copied or awaited inside the loop; after it, one copy of the store
+writes the SAME predictions json byte for byte and the AP is matched from device memory without re-reading that file.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
 """
 import json
 import os
@@ -24,9 +30,11 @@ from counting_detr_amd.misc import NestedTensor
 
 
 @torch.no_grad()
-def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True):
+def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
-    runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager)."""
+    runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
+    `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
+    (the split's instances json) the metrics also carry the box AP, matched from the device-resident detections."""
     output_path = os.path.join(output_dir, "predictions_" + split + ".json")
     if os.path.isfile(output_path):
         os.remove(output_path)
@@ -34,6 +42,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     criterion.eval()
     from counting_detr_amd.engine import InferenceEngine
     engine = InferenceEngine(model, threshold, graphs=graphs and torch.device(device).type == "cuda", device=device)
+    if device_detections:
+        return _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json)
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
     pred_counts, gt_counts, loss_sum, n_img = [], [], {}, 0
@@ -84,6 +94,84 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     return metrics, predictions
 
 
+def _num_images(data_loader):
+    """Images a loader will yield (the device store is allocated once, up front)."""
+    inner = getattr(data_loader, "loader", data_loader)                 # data.Prefetcher wraps the DataLoader
+    if hasattr(inner, "dataset"):
+        return len(inner.dataset)
+    if isinstance(inner, (list, tuple)):
+        return sum(int(b["image"].shape[0]) for b in inner)
+    raise RuntimeError("infer: device_detections needs the number of images up front (a DataLoader, a data.Prefetcher or a list of batches)")
+
+
+def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json):
+    """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer, one
+    cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
+    and image ids into a device table.  After the loop: one copy each of the store, the table and the loss buffer; the json is written from the
+    store's arrays (same bytes as the host loop's file), the losses are summed in Python in the same order (same floats), the counts are the
+    store's, and the AP (`gt_json`) is coco_ap.summarize_store on the store -- the file is not read back."""
+    import numpy as np
+    from counting_detr_amd import ops
+    from counting_detr_amd.coco_ap import MAX_DETS, gt_from_json, summarize_store
+    if device.type != "cuda":
+        raise RuntimeError(f"infer: device_detections runs HIP kernels, device={device} has none (the default is the host path)")
+    N = _num_images(data_loader)
+    store = meta = loss_buf = loss_keys = None
+    n_targets, gt_counts, n_img, n_batch = [], [], 0, 0
+    with torch.cuda.device(device):
+        for ret in data_loader:
+            image, mask = ret["image"].to(device), ret["mask"].to(device)
+            rects = ret["ex_rects"].to(device)
+            targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
+            _, _, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects)
+            loss_dict = criterion(outputs, targets)
+            B, Q = prob.shape
+            if store is None:
+                store = ops.DetectionStore(N, Q, device, threshold=threshold, max_det=MAX_DETS)
+                meta = torch.zeros((N, 3), dtype=torch.int64, device=device)                # ori_h, ori_w, image id
+                loss_keys = list(loss_dict)
+                loss_buf = torch.zeros((N, len(loss_keys)), dtype=torch.float64, device=device)      # fp32 -> fp64 is exact: float(v) of the host loop
+            if n_img + B > N or list(loss_dict) != loss_keys:
+                raise RuntimeError(f"infer: the loader yields more than its {N} images, or the criterion changed its losses")
+            loss_buf[n_batch].copy_(torch.stack([v.detach().reshape(()).to(torch.float64) for v in loss_dict.values()]))
+            rows = meta[n_img:n_img + B]
+            rows[:, :2].copy_(torch.as_tensor(ret["orig_size"]).reshape(B, 2), non_blocking=True)
+            if "image_id" in ret:
+                rows[:, 2].copy_(torch.as_tensor(ret["image_id"]).reshape(B), non_blocking=True)
+            else:
+                rows[:, 2].copy_(torch.arange(n_img, n_img + B))
+            store.emit(prob.contiguous(), outputs["pred_boxes"].contiguous(), ref_points.reshape(B, Q, 2).contiguous(), rows[:, :2].to(torch.int32))
+            n_targets.append(len(targets))
+            gt_counts += [int(t["boxes"].shape[0]) for t in targets]
+            n_img += B
+            n_batch += 1
+        predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
+        loss_sum, pred_counts, image_ids = {}, [], []
+        if n_img:
+            host = store.finish()
+            meta_h = meta[:n_img].cpu().tolist()
+            for row, n_t in zip(loss_buf[:n_batch].cpu().tolist(), n_targets):
+                for k, v in zip(loss_keys, row):
+                    loss_sum[k] = loss_sum.get(k, 0.0) + v * n_t
+            pred_counts = host["counts"].tolist()
+            image_ids = [m[2] for m in meta_h]
+            per_image = np.diff(host["wire_off"]).tolist()
+            ann_image = [i for i, c in zip(image_ids, per_image) for _ in range(c)]
+            wire, score = host["wire"].tolist(), host["score"].astype(np.float64).tolist()
+            predictions["annotations"] = [{"id": k + 1, "image_id": i, "area": w[4], "bbox": w[:4], "category_id": 1, "score": sc, "point": w[5:7]}
+                                          for k, (i, w, sc) in enumerate(zip(ann_image, wire, score))]
+            predictions["images"] = [{"id": m[2], "height": m[0], "width": m[1], "file_name": "None"} for m in meta_h]
+        with open(output_path, "w") as handle:
+            json.dump(predictions, handle)
+        metrics = {k: v / max(n_img, 1) for k, v in loss_sum.items()}
+        if n_img:
+            metrics.update(counting_metrics(pred_counts, gt_counts))
+        metrics["images"] = n_img
+        if gt_json is not None and n_img:
+            metrics.update(summarize_store(gt_from_json(gt_json, image_ids), store, image_ids))
+    return metrics, predictions
+
+
 def counting_metrics_from_json(pred_json, gt_json, threshold=0.5):
     """MAE / RMSE / NAE / SRE from a predictions json and the split's `instances_<split>.json` (A2/eval_all.py:141-270:
     predicted count = #annotations with score >= threshold per image, ground truth = #instances)."""
@@ -112,9 +200,12 @@ def main(args):
     if raw:
         dl = data.Prefetcher(dl, device)
     os.makedirs(args.output_dir, exist_ok=True)
-    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split)
     gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
-    if os.path.isfile(gt_json):
+    on_device = bool(getattr(args, "device_detections", False))
+    ap_in_loop = on_device and os.path.isfile(gt_json) and not getattr(args, "ap_on_host", False)      # matched from the device-resident detections
+    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
+                       gt_json=gt_json if ap_in_loop else None)
+    if os.path.isfile(gt_json) and not ap_in_loop:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
         ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None

@@ -129,7 +129,10 @@ def main(args):
                             collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers)
             if raw:
                 dl = data.Prefetcher(dl, device)
-            metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split)
+            on_device = bool(getattr(args, "device_detections", False))      # post-forward work + box AP on the device (infer.py)
+            gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+            metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
+                                      gt_json=gt_json if on_device and os.path.isfile(gt_json) else None)
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
