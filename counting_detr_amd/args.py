@@ -109,7 +109,11 @@ def get_args_parser_stage1():
     p.add_argument("--lr_backbone", default=1e-5, type=float)
     p.add_argument("--lr_linear_proj_names", default=[], type=str, nargs="+")
     p.add_argument("--lr_linear_proj_mult", default=0.1, type=float)
-    p.add_argument("--batch_size", default=1, type=int, help="images per step (the reference: 1; more need equal exemplar counts)")
+    p.add_argument("--batch_size", default=1, type=int,
+                   help="images per step (the reference: 1; more need equal exemplar counts, or --ragged_batches)")
+    p.add_argument("--ragged_batches", action="store_true",
+                   help="batches may mix images with different numbers of points (padded, per-image counts on the device): training and --eval "
+                        "with any --batch_size; --generate_pseudo_label runs --batch_size same-sized images per forward")
     p.add_argument("--weight_decay", default=1e-4, type=float)
     p.add_argument("--epochs", default=30, type=int)
     p.add_argument("--lr_drop", default=20, type=int)

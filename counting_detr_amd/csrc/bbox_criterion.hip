@@ -91,17 +91,37 @@ __host__ __device__ __forceinline__ BcPair bc_pair(float cx, float cy, float pw,
     return r;
 }
 
+// valid rows of image b: clamp(lens[b], 0, N)
+__device__ __forceinline__ int bc_len(const int32_t* __restrict__ lens, int b, int N) { return min(max(lens[b], 0), N); }
+
+// LENS (cdetr_bbox_criterion_lens_*): `rows` = B*N rows of B images, row n of image b is a pair iff n < lens[b]; the normaliser M = sum(lens) is
+// formed HERE from device memory (every thread sums the same B words in the same order), so a captured graph follows new counts.  A padded
+// row is skipped by branch -- its prediction and targets are never read -- and gets exact-zero gradients.  The pair -> thread map is the
+// dense kernel's over B*N, so with every lens[b] == N each partial sum, and the result, is the dense kernel's bit for bit.
+template <bool LENS>
 __global__ __launch_bounds__(BC_THREADS) void bbox_criterion_fwd_kernel(const float* __restrict__ pred_wh, const int64_t pred_stride,
                                                                          const float* __restrict__ tgt_points, const float* __restrict__ tgt_whs,
-                                                                         const int M, const float w_wh, const float w_giou,
+                                                                         const int rows, const float w_wh, const float w_giou,
                                                                          float* __restrict__ losses, float* __restrict__ g_wh,
-                                                                         float* __restrict__ g_giou) {
+                                                                         float* __restrict__ g_giou, const int32_t* __restrict__ lens, const int N) {
     __builtin_amdgcn_s_setprio(3);                   // one workgroup on the step's critical path (as criterion_fwd_kernel)
     __shared__ float wred[2][BC_WAVES];
     const int tid = threadIdx.x;
-    const float inv_2m = 1.f / (float)(2 * M), inv_m = 1.f / (float)M;
+    int M = rows;
+    if constexpr (LENS) {
+        M = 0;
+        for (int b = 0; b < rows / N; ++b) M += bc_len(lens, b, N);
+    }
+    const bool any = !LENS || M > 0;
+    const float inv_2m = any ? 1.f / (float)(2 * M) : 0.f, inv_m = any ? 1.f / (float)M : 0.f;
     float l1 = 0.f, gl = 0.f;
-    for (int i = tid; i < M; i += BC_THREADS) {      // fixed pair -> thread map: the partial sums do not depend on timing
+    for (int i = tid; i < rows; i += BC_THREADS) {   // fixed pair -> thread map: the partial sums do not depend on timing
+        if constexpr (LENS) {
+            if (i % N >= bc_len(lens, i / N, N)) {
+                g_wh[2 * i] = 0.f; g_wh[2 * i + 1] = 0.f; g_giou[2 * i] = 0.f; g_giou[2 * i + 1] = 0.f;
+                continue;
+            }
+        }
         const float* p = pred_wh + (int64_t)i * pred_stride;
         const BcPair r = bc_pair(tgt_points[2 * i], tgt_points[2 * i + 1], p[0], p[1], tgt_whs[2 * i], tgt_whs[2 * i + 1]);
         l1 += r.l1;
@@ -124,7 +144,7 @@ __global__ __launch_bounds__(BC_THREADS) void bbox_criterion_fwd_kernel(const fl
             s1 += wred[0][w];
             s2 += wred[1][w];
         }
-        const float lwh = s1 / (float)(2 * M), lgi = s2 / (float)M;
+        const float lwh = any ? s1 / (float)(2 * M) : 0.f, lgi = any ? s2 / (float)M : 0.f;
         losses[0] = lwh;
         losses[1] = lgi;
         losses[2] = __fadd_rn(__fmul_rn(lwh, w_wh), __fmul_rn(lgi, w_giou));      // (no contraction: the host-side sum's rounding)
@@ -132,13 +152,24 @@ __global__ __launch_bounds__(BC_THREADS) void bbox_criterion_fwd_kernel(const fl
 }
 
 // d_coord [M][4] = (0, 0, e_wh * g_wh + e_giou * g_giou) with e_k = g3[k] + g3[2] * w_k
+template <bool LENS>
 __global__ __launch_bounds__(BC_THREADS) void bbox_criterion_bwd_kernel(const float* __restrict__ g3, const float w_wh, const float w_giou,
                                                                          const float* __restrict__ g_wh, const float* __restrict__ g_giou,
-                                                                         float* __restrict__ d_coord, const int M) {
+                                                                         float* __restrict__ d_coord, const int M,
+                                                                         const int32_t* __restrict__ lens, const int N) {
     const float e_wh = __fadd_rn(g3[0], __fmul_rn(g3[2], w_wh)), e_gi = __fadd_rn(g3[1], __fmul_rn(g3[2], w_giou));
     for (int i = blockIdx.x * BC_THREADS + threadIdx.x; i < M; i += gridDim.x * BC_THREADS) {
-        const float dw = __fadd_rn(__fmul_rn(e_wh, g_wh[2 * i]), __fmul_rn(e_gi, g_giou[2 * i]));
-        const float dh = __fadd_rn(__fmul_rn(e_wh, g_wh[2 * i + 1]), __fmul_rn(e_gi, g_giou[2 * i + 1]));
+        if constexpr (LENS) {
+            if (i % N >= bc_len(lens, i / N, N)) {   // padded pair: exact zeros whatever the upstream gradient holds
+                *reinterpret_cast<float4*>(d_coord + 4 * (int64_t)i) = make_float4(0.f, 0.f, 0.f, 0.f);
+                continue;
+            }
+        }
+        // e_wh g_wh + e_gi g_giou with the roundings spelled out: one product rounds, the other is fused into the sum -- which one, per
+        // column, is what the compiler made of the plain product-sum in the dense kernel all along (the intrinsics contract); written as
+        // fmaf so that both instantiations round alike whatever surrounds them
+        const float dw = fmaf(e_wh, g_wh[2 * i], e_gi * g_giou[2 * i]);
+        const float dh = fmaf(e_gi, g_giou[2 * i + 1], e_wh * g_wh[2 * i + 1]);
         *reinterpret_cast<float4*>(d_coord + 4 * (int64_t)i) = make_float4(0.f, 0.f, dw, dh);
     }
 }
@@ -150,8 +181,8 @@ extern "C" int cdetr_bbox_criterion_fwd(const float* pred_wh, int64_t pred_strid
     CDETR_CHECK_ARG(pred_wh && tgt_points && tgt_whs && losses && g_wh && g_giou, "cdetr_bbox_criterion_fwd: null pointer");
     CDETR_CHECK_ARG(M > 0 && M <= (1 << 28) && pred_stride >= 2, "cdetr_bbox_criterion_fwd: bad sizes (M %d, pred_stride %lld)", M,
                     (long long)pred_stride);
-    hipLaunchKernelGGL(bbox_criterion_fwd_kernel, dim3(1), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), pred_wh, pred_stride,
-                       tgt_points, tgt_whs, M, w_wh, w_giou, losses, g_wh, g_giou);
+    hipLaunchKernelGGL(bbox_criterion_fwd_kernel<false>, dim3(1), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), pred_wh, pred_stride,
+                       tgt_points, tgt_whs, M, w_wh, w_giou, losses, g_wh, g_giou, nullptr, 1);
     return cdetr_launch_status("cdetr_bbox_criterion_fwd");
 }
 
@@ -161,7 +192,31 @@ extern "C" int cdetr_bbox_criterion_bwd(const float* g3, float w_wh, float w_gio
     CDETR_CHECK_ARG((reinterpret_cast<uintptr_t>(d_coord) & 15) == 0, "cdetr_bbox_criterion_bwd: d_coord must be 16-byte aligned");
     int blocks = (M + BC_THREADS - 1) / BC_THREADS;
     if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(bbox_criterion_bwd_kernel, dim3(blocks), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), g3, w_wh, w_giou,
-                       g_wh, g_giou, d_coord, M);
+    hipLaunchKernelGGL(bbox_criterion_bwd_kernel<false>, dim3(blocks), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), g3, w_wh, w_giou,
+                       g_wh, g_giou, d_coord, M, nullptr, 1);
     return cdetr_launch_status("cdetr_bbox_criterion_bwd");
+}
+
+extern "C" int cdetr_bbox_criterion_lens_fwd(const float* pred_wh, int64_t pred_stride, const float* tgt_points, const float* tgt_whs,
+                                             const int32_t* lens, int32_t B, int32_t N, float w_wh, float w_giou, float* losses, float* g_wh,
+                                             float* g_giou, void* stream) {
+    CDETR_CHECK_ARG(pred_wh && tgt_points && tgt_whs && lens && losses && g_wh && g_giou, "cdetr_bbox_criterion_lens_fwd: null pointer");
+    CDETR_CHECK_ARG(B > 0 && N > 0 && (int64_t)B * N <= (1 << 28) && pred_stride >= 2,
+                    "cdetr_bbox_criterion_lens_fwd: bad sizes (B %d, N %d, pred_stride %lld)", B, N, (long long)pred_stride);
+    hipLaunchKernelGGL(bbox_criterion_fwd_kernel<true>, dim3(1), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), pred_wh, pred_stride,
+                       tgt_points, tgt_whs, B * N, w_wh, w_giou, losses, g_wh, g_giou, lens, N);
+    return cdetr_launch_status("cdetr_bbox_criterion_lens_fwd");
+}
+
+extern "C" int cdetr_bbox_criterion_lens_bwd(const float* g3, float w_wh, float w_giou, const float* g_wh, const float* g_giou,
+                                             const int32_t* lens, float* d_coord, int32_t B, int32_t N, void* stream) {
+    CDETR_CHECK_ARG(g3 && g_wh && g_giou && lens && d_coord, "cdetr_bbox_criterion_lens_bwd: null pointer");
+    CDETR_CHECK_ARG(B > 0 && N > 0 && (int64_t)B * N <= (1 << 28), "cdetr_bbox_criterion_lens_bwd: bad sizes (B %d, N %d)", B, N);
+    CDETR_CHECK_ARG((reinterpret_cast<uintptr_t>(d_coord) & 15) == 0, "cdetr_bbox_criterion_lens_bwd: d_coord must be 16-byte aligned");
+    const int M = B * N;
+    int blocks = (M + BC_THREADS - 1) / BC_THREADS;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(bbox_criterion_bwd_kernel<true>, dim3(blocks), dim3(BC_THREADS), 0, reinterpret_cast<hipStream_t>(stream), g3, w_wh, w_giou,
+                       g_wh, g_giou, d_coord, M, lens, N);
+    return cdetr_launch_status("cdetr_bbox_criterion_lens_bwd");
 }

@@ -15,6 +15,8 @@
 // their own row strides.  cdetr_mha_* is the instance q = qk, k = qk + E (ldq = ldk = 2E), Lq = Lk = L: the same arithmetic, addresses only
 // computed differently.  The encoder's self-attention over h*w tokens and the decoder's cross-attention from Q queries to h*w keys of the
 // nn.MultiheadAttention variant (A2/models/transformer.py:262-272,393-398) run on the same kernels.
+// cdetr_mha_*_lens (stage 1's ragged batches: image n holds lens[n] <= L queries, the rest is padding) is the LENS instantiation of the same
+// bodies: addresses by L, every masking bound by the per-image length read from device memory (see image_len below).
 #include "../../include/cdetr_hip.h"
 #include "common.h"
 #include <stdlib.h>
@@ -60,9 +62,19 @@ __device__ __forceinline__ void load_tile(float* __restrict__ dst, const float* 
     }
 }
 
+// cdetr_mha_*_lens: image n's rows still start at n * L, only the masking bound becomes len = clamp(lens[n], 0, L) on the query AND the key side
+// (one scalar per workgroup: uniform per blockIdx.y).  Every kernel below takes the row counts twice: Sq / Sk address the images, Lq / Lk
+// bound the rows; the dense instantiations (LENS = false) set Lq = Sq, Lk = Sk and are the code they were.
+template <bool LENS>
+__device__ __forceinline__ int image_len(const int32_t* __restrict__ lens, int n, int L) {
+    if constexpr (LENS) return min(max(lens[n], 0), L);
+    else return L;
+}
+
+template <bool LENS>
 __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                       const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
-                                                      int Lq, int Lk, int nh, float scale) {
+                                                      int Sq, int Sk, int nh, float scale, const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) float Ks[KT * D];
     __shared__ __attribute__((aligned(16))) float Vs[KT * D];
     const int E = nh * D;
@@ -70,10 +82,20 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ 
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 64 + wid * 16 + i32;
+    const int Lq = image_len<LENS>(lens, n, Sq), Lk = LENS ? Lq : Sk;
     const bool qv = q < Lq;
-    const float* qn = qg + (long)n * Lq * ldq;
-    const float* kn = kg + (long)n * Lk * ldk;
-    const float* vn = vg + (long)n * Lk * ldv;
+    if constexpr (LENS) {
+        if (!qv && q < Sq) {                       // padded query: exact zeros, nothing left uninitialised
+            float* op = o + ((long)n * Sq + q) * E + head * D + g * 8;
+            *reinterpret_cast<float4*>(op) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(op + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (g == 0) lse[((long)n * nh + head) * Sq + q] = 0.f;
+        }
+        if ((int)blockIdx.x * 64 >= Lq) return;    // workgroup-uniform, before any barrier
+    }
+    const float* qn = qg + (long)n * Sq * ldq;
+    const float* kn = kg + (long)n * Sk * ldk;
+    const float* vn = vg + (long)n * Sk * ldv;
     float qr[D];
     {
         const float* qp = qn + (long)(qv ? q : 0) * ldq + head * D;
@@ -134,20 +156,22 @@ __global__ __launch_bounds__(256) void mha_fwd_kernel(const float* __restrict__ 
         acc[c] = a * inv;
     }
     if (qv) {
-        float* op = o + ((long)n * Lq + q) * E + head * D + g * 8;     // each lane group writes 8 channels
+        float* op = o + ((long)n * Sq + q) * E + head * D + g * 8;     // each lane group writes 8 channels
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4)
             *reinterpret_cast<float4*>(op + c4 * 4) = make_float4(acc[g * 8 + c4 * 4 + 0], acc[g * 8 + c4 * 4 + 1],
                                                                   acc[g * 8 + c4 * 4 + 2], acc[g * 8 + c4 * 4 + 3]);
-        if (g == 0) lse[((long)n * nh + head) * Lq + q] = mn + logf(l);
+        if (g == 0) lse[((long)n * nh + head) * Sq + q] = mn + logf(l);
     }
 }
 
 // dq[i] = scale * sum_j p_ij (dO_i.v_j - D_i) k_j,   D_i = dO_i . O_i   (lanes own queries)
+template <bool LENS>
 __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                         const float* __restrict__ vg, long ldv, const float* __restrict__ o,
                                                         const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dq_out,
-                                                        long lddq, float* __restrict__ Dbuf, int Lq, int Lk, int nh, float scale) {
+                                                        long lddq, float* __restrict__ Dbuf, int Sq, int Sk, int nh, float scale,
+                                                        const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) float Ks[KT * D];
     __shared__ __attribute__((aligned(16))) float Vs[KT * D];
     const int E = nh * D;
@@ -155,14 +179,23 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 64 + wid * 16 + i32;
+    const int Lq = image_len<LENS>(lens, n, Sq), Lk = LENS ? Lq : Sk;
     const bool qv = q < Lq;
-    const float* qn = qg + (long)n * Lq * ldq;
-    const float* kn = kg + (long)n * Lk * ldk;
-    const float* vn = vg + (long)n * Lk * ldv;
+    if constexpr (LENS) {
+        if (!qv && q < Sq) {                       // padded query: d_q is exact zero
+            float* out = dq_out + ((long)n * Sq + q) * lddq + head * D + g * 8;
+            *reinterpret_cast<float4*>(out) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(out + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if ((int)blockIdx.x * 64 >= Lq) return;    // workgroup-uniform, before any barrier
+    }
+    const float* qn = qg + (long)n * Sq * ldq;
+    const float* kn = kg + (long)n * Sk * ldk;
+    const float* vn = vg + (long)n * Sk * ldv;
     float qr[D], dor[D], dq[D];
     float Di = 0.f;
     {
-        const long row = (long)n * Lq + (qv ? q : 0);
+        const long row = (long)n * Sq + (qv ? q : 0);
         const float* qp = qn + (long)(qv ? q : 0) * ldq + head * D;
         const float* dp = dO + row * E + head * D;
         const float* op = o + row * E + head * D;
@@ -176,7 +209,7 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < D; ++c) dq[c] = 0.f;
     }
-    const float li = qv ? lse[((long)n * nh + head) * Lq + q] : 0.f;
+    const float li = qv ? lse[((long)n * nh + head) * Sq + q] : 0.f;
     for (int k0 = 0; k0 < Lk; k0 += KT) {
         __syncthreads();
         load_tile(Ks, kn, ldk, head * D, k0, Lk);
@@ -197,21 +230,22 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float* __restrict_
         dq[c] = a * scale;
     }
     if (qv) {
-        float* out = dq_out + ((long)n * Lq + q) * lddq + head * D;
+        float* out = dq_out + ((long)n * Sq + q) * lddq + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4)
             *reinterpret_cast<float4*>(out + g * 8 + c4 * 4) = make_float4(dq[g * 8 + c4 * 4 + 0], dq[g * 8 + c4 * 4 + 1],
                                                                            dq[g * 8 + c4 * 4 + 2], dq[g * 8 + c4 * 4 + 3]);
-        if (g == 0) Dbuf[((long)n * nh + head) * Lq + q] = Di;
+        if (g == 0) Dbuf[((long)n * nh + head) * Sq + q] = Di;
     }
 }
 
 // dk[j] = scale * sum_i p_ij (dO_i.v_j - D_i) q_i,   dv[j] = sum_i p_ij dO_i   (lanes own keys, query tiles through LDS)
+template <bool LENS>
 __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                          const float* __restrict__ vg, long ldv, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, const float* __restrict__ Dbuf,
                                                          float* __restrict__ dk_out, long lddk, float* __restrict__ dv, long lddv,
-                                                         int Lq, int Lk, int nh, float scale) {
+                                                         int Sq, int Sk, int nh, float scale, const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) float Qs[KT * D];
     __shared__ __attribute__((aligned(16))) float Os[KT * D];
     __shared__ float Ls[KT], Dsh[KT];
@@ -220,13 +254,25 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
     const int i32 = lane & 15, g = lane >> 4;      // 16 rows per wave, 4-way split of the reduction axis
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int j = blockIdx.x * 64 + wid * 16 + i32;
+    const int Lq = image_len<LENS>(lens, n, Sq), Lk = LENS ? Lq : Sk;
     const bool jv = j < Lk;
-    const float* qn = qg + (long)n * Lq * ldq;
-    const float* don = dO + (long)n * Lq * E;
+    if constexpr (LENS) {
+        if (!jv && j < Sk) {                       // padded key: d_k and d_v are exact zeros
+            float* ok = dk_out + ((long)n * Sk + j) * lddk + head * D + g * 8;
+            float* ov = dv + ((long)n * Sk + j) * lddv + head * D + g * 8;
+            *reinterpret_cast<float4*>(ok) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(ok + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(ov) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(ov + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if ((int)blockIdx.x * 64 >= Lk) return;    // workgroup-uniform, before any barrier
+    }
+    const float* qn = qg + (long)n * Sq * ldq;
+    const float* don = dO + (long)n * Sq * E;
     float kr[D], vr[D], dk[D], dvv[D];
     {
-        const float* kp = kg + ((long)n * Lk + (jv ? j : 0)) * ldk + head * D;
-        const float* vp = vg + ((long)n * Lk + (jv ? j : 0)) * ldv + head * D;
+        const float* kp = kg + ((long)n * Sk + (jv ? j : 0)) * ldk + head * D;
+        const float* vp = vg + ((long)n * Sk + (jv ? j : 0)) * ldv + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 8; ++c4) {
             const float4 t = ld4(kp + c4 * 4), u = ld4(vp + c4 * 4);
@@ -242,8 +288,8 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
         load_tile(Os, don, E, head * D, q0, Lq);
         for (int r = threadIdx.x; r < KT; r += blockDim.x) {
             const bool ok = q0 + r < Lq;
-            Ls[r] = ok ? lse[((long)n * nh + head) * Lq + q0 + r] : INFINITY;    // p = exp(s - inf) = 0 beyond Lq
-            Dsh[r] = ok ? Dbuf[((long)n * nh + head) * Lq + q0 + r] : 0.f;
+            Ls[r] = ok ? lse[((long)n * nh + head) * Sq + q0 + r] : INFINITY;    // p = exp(s - inf) = 0 beyond Lq
+            Dsh[r] = ok ? Dbuf[((long)n * nh + head) * Sq + q0 + r] : 0.f;
         }
         __syncthreads();
         const int nq = min(KT, Lq - q0);
@@ -265,8 +311,8 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict
         dvv[c] = b;
     }
     if (jv) {
-        float* ok = dk_out + ((long)n * Lk + j) * lddk + head * D + g * 8;
-        float* ov = dv + ((long)n * Lk + j) * lddv + head * D + g * 8;
+        float* ok = dk_out + ((long)n * Sk + j) * lddk + head * D + g * 8;
+        float* ov = dv + ((long)n * Sk + j) * lddv + head * D + g * 8;
 #pragma unroll
         for (int c4 = 0; c4 < 2; ++c4) {
             *reinterpret_cast<float4*>(ok + c4 * 4) = make_float4(dk[g * 8 + c4 * 4 + 0], dk[g * 8 + c4 * 4 + 1],
@@ -367,18 +413,30 @@ __device__ __forceinline__ void store_own(float* __restrict__ row, int g, const 
 }
 __device__ __forceinline__ f32x16 zero16() { return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
 
+// a padded row (len <= row < L) of a lens launch: this lane's 16 of the row's 32 columns as exact zeros
+__device__ __forceinline__ void zero_own(float* __restrict__ row, int g) { store_own(row, g, zero16(), 0.f); }
+
+template <bool LENS>
 __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                   const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
-                                                  int Lq, int Lk, int nh, float scale) {
+                                                  int Sq, int Sk, int nh, float scale, const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) __bf16 lds[2 * 2 * TILE];          // [buf][K | V^T]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const float* kn = kg + (long)n * Lk * ldk;
-    const float* vn = vg + (long)n * Lk * ldv;
+    const int Lq = image_len<LENS>(lens, n, Sq), Lk = LENS ? Lq : Sk;
+    if constexpr (LENS) {
+        if (q >= Lq && q < Sq) {
+            zero_own(o + ((long)n * Sq + q) * E + head * D, g);
+            if (g == 0) lse[((long)n * nh + head) * Sq + q] = 0.f;
+        }
+        if ((int)blockIdx.x * 32 * NWF >= Lq) return;                          // workgroup-uniform, before any barrier
+    }
+    const float* kn = kg + (long)n * Sk * ldk;
+    const float* vn = vg + (long)n * Sk * ldv;
     bf16x8 qh[2], ql[2];
-    own_frag(qg + ((long)n * Lq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
+    own_frag(qg + ((long)n * Sq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
     float m = -INFINITY, l = 0.f;
     f32x16 OT = zero16();
     constexpr int PD = 3;                                                      // tiles in flight (register ring, statically indexed)
@@ -432,8 +490,8 @@ __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qg, 
         step(r2, r0, t0 + 2);
     }
     if (q < Lq) {
-        store_own(o + ((long)n * Lq + q) * E + head * D, g, OT, 1.f / l);
-        if (g == 0) lse[((long)n * nh + head) * Lq + q] = m + logf(l);
+        store_own(o + ((long)n * Sq + q) * E + head * D, g, OT, 1.f / l);
+        if (g == 0) lse[((long)n * nh + head) * Sq + q] = m + logf(l);
     }
 }
 
@@ -441,9 +499,10 @@ __global__ __launch_bounds__(NTF) void fwd_kernel(const float* __restrict__ qg, 
 // the second half, for the same 2 x 32 queries -- and merge their (running maximum, sum, O^T) through LDS at the end.  A wave's life is a chain of
 // [barrier, two dependent MFMA groups, a softmax update] per key tile with nobody to overlap with (160 waves on 1024 SIMDs at L = 300): half the steps per
 // wave.  Each half stages its own tiles (its two waves = the 128 staging threads of fwd_kernel), both halves share the barriers.
+template <bool LENS>
 __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                          const float* __restrict__ vg, long ldv, float* __restrict__ o, float* __restrict__ lse,
-                                                         int Lq, int Lk, int nh, float scale) {
+                                                         int Sq, int Sk, int nh, float scale, const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) __bf16 lds_all[2 * 2 * 2 * TILE];      // [key half][buf][K | V^T]
     const int E = nh * D;
     const int tid = threadIdx.x & (NTF - 1), lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
@@ -451,10 +510,18 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
     __bf16* lds = lds_all + kh * (2 * 2 * TILE);
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
-    const float* kn = kg + (long)n * Lk * ldk;
-    const float* vn = vg + (long)n * Lk * ldv;
+    const int Lq = image_len<LENS>(lens, n, Sq), Lk = LENS ? Lq : Sk;
+    if constexpr (LENS) {
+        if (kh == 0 && q >= Lq && q < Sq) {
+            zero_own(o + ((long)n * Sq + q) * E + head * D, g);
+            if (g == 0) lse[((long)n * nh + head) * Sq + q] = 0.f;
+        }
+        if ((int)blockIdx.x * 32 * NWF >= Lq) return;                          // workgroup-uniform, before any barrier
+    }
+    const float* kn = kg + (long)n * Sk * ldk;
+    const float* vn = vg + (long)n * Sk * ldv;
     bf16x8 qh[2], ql[2];
-    own_frag(qg + ((long)n * Lq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
+    own_frag(qg + ((long)n * Sq + min(q, Lq - 1)) * ldq + head * D, g, scale, qh, ql);
     float m = -INFINITY, l = 0.f;
     f32x16 OT = zero16();
     constexpr int PD = 3;
@@ -523,8 +590,8 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
         f32x16 OM;
 #pragma unroll
         for (int r = 0; r < 16; ++r) OM[r] = OT[r] * c1 + mrg[2 + r] * c2;
-        store_own(o + ((long)n * Lq + q) * E + head * D, g, OM, 1.f / lt);
-        if (g == 0) lse[((long)n * nh + head) * Lq + q] = mn + logf(lt);
+        store_own(o + ((long)n * Sq + q) * E + head * D, g, OM, 1.f / lt);
+        if (g == 0) lse[((long)n * nh + head) * Sq + q] = mn + logf(lt);
     }
 }
 
@@ -539,30 +606,30 @@ __global__ __launch_bounds__(2 * NTF) void fwd_ks_kernel(const float* __restrict
 template <int TB>
 __device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                            const float* __restrict__ vg, long ldv, const float* __restrict__ o, const float* __restrict__ dO,
-                                           const float* __restrict__ lse, float* __restrict__ dq_out, long lddq, int Lq, int Lk, int nh,
-                                           float scale) {
+                                           const float* __restrict__ lse, float* __restrict__ dq_out, long lddq, int Sq, int Sk, int Lq,
+                                           int Lk, int nh, float scale) {
     // lds: [buf][K | V | K^T]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int q = blockIdx.x * 32 * NWF + wid * 32 + i32;
     const int qc = min(q, Lq - 1);
-    const float* kn = kg + (long)n * Lk * ldk;
-    const float* vn = vg + (long)n * Lk * ldv;
+    const float* kn = kg + (long)n * Sk * ldk;
+    const float* vn = vg + (long)n * Sk * ldv;
     bf16x8 qh[2], ql[2], dh[2], dl[2];
-    own_frag(qg + ((long)n * Lq + qc) * ldq + head * D, g, scale, qh, ql);
-    const float* dop = dO + ((long)n * Lq + qc) * E + head * D;
+    own_frag(qg + ((long)n * Sq + qc) * ldq + head * D, g, scale, qh, ql);
+    const float* dop = dO + ((long)n * Sq + qc) * E + head * D;
     own_frag(dop, g, 1.f, dh, dl);
     float Di = 0.f;
     {
-        const float* op = o + ((long)n * Lq + qc) * E + head * D;
+        const float* op = o + ((long)n * Sq + qc) * E + head * D;
 #pragma unroll
         for (int c4 = 0; c4 < 8; ++c4) {
             const float4 u = ld4(dop + c4 * 4), w = ld4(op + c4 * 4);
             Di += (u.x * w.x + u.y * w.y) + (u.z * w.z + u.w * w.w);
         }
     }
-    const float li = lse[((long)n * nh + head) * Lq + qc];
+    const float li = lse[((long)n * nh + head) * Sq + qc];
     f32x16 dQT = zero16();
     constexpr int PD = 3;
     struct Ring { NatRegs k, v; TrRegs kt; } r0, r1, r2;
@@ -607,7 +674,7 @@ __device__ __forceinline__ void bwd_q_body(__bf16* lds, const float* __restrict_
         step(r2, r0, t0 + 2);
     }
     if (q < Lq) {
-        store_own(dq_out + ((long)n * Lq + q) * lddq + head * D, g, dQT, scale);
+        store_own(dq_out + ((long)n * Sq + q) * lddq + head * D, g, dQT, scale);
     }
 }
 
@@ -615,21 +682,21 @@ template <int TB>
 __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], const float* __restrict__ qg, long ldq,
                                             const float* __restrict__ kg, long ldk, const float* __restrict__ vg, long ldv,
                                             const float* __restrict__ o, const float* __restrict__ dO, const float* __restrict__ lse,
-                                            float* __restrict__ dk_out, long lddk, float* __restrict__ dv, long lddv, int Lq, int Lk, int nh,
-                                            float scale) {
+                                            float* __restrict__ dk_out, long lddk, float* __restrict__ dv, long lddv, int Sq, int Sk, int Lq,
+                                            int Lk, int nh, float scale) {
     // lds: [buf][Q | dO | Q^T | dO^T]; stat: [buf][lse | D][query of the tile]
     const int E = nh * D;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, g = lane >> 5;
     const int n = blockIdx.y / nh, head = blockIdx.y % nh;
     const int j = blockIdx.x * 32 * NWF + wid * 32 + i32;
     const int jc = min(j, Lk - 1);
-    const float* qn = qg + (long)n * Lq * ldq;
-    const float* don = dO + (long)n * Lq * E;
-    const float* on = o + (long)n * Lq * E;
-    const float* lsn = lse + ((long)n * nh + head) * Lq;
+    const float* qn = qg + (long)n * Sq * ldq;
+    const float* don = dO + (long)n * Sq * E;
+    const float* on = o + (long)n * Sq * E;
+    const float* lsn = lse + ((long)n * nh + head) * Sq;
     bf16x8 kh[2], kl[2], vh[2], vl[2];
-    own_frag(kg + ((long)n * Lk + jc) * ldk + head * D, g, scale, kh, kl);
-    own_frag(vg + ((long)n * Lk + jc) * ldv + head * D, g, 1.f, vh, vl);
+    own_frag(kg + ((long)n * Sk + jc) * ldk + head * D, g, scale, kh, kl);
+    own_frag(vg + ((long)n * Sk + jc) * ldv + head * D, g, 1.f, vh, vl);
     f32x16 dKT = zero16(), dVT = zero16();
     constexpr int PD = 3;
     const float* trsrc = (wid == 0) ? qn : don;                                // wave 0 stages Q^T, wave 1 dO^T
@@ -701,25 +768,35 @@ __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], c
         step(r2, r0, t0 + 2);
     }
     if (j < Lk) {
-        store_own(dk_out + ((long)n * Lk + j) * lddk + head * D, g, dKT, scale);
-        store_own(dv + ((long)n * Lk + j) * lddv + head * D, g, dVT, 1.f);
+        store_own(dk_out + ((long)n * Sk + j) * lddk + head * D, g, dKT, scale);
+        store_own(dv + ((long)n * Sk + j) * lddv + head * D, g, dVT, 1.f);
     }
 }
 
 // With Lq != Lk the grid is as wide as the longer side: the surplus workgroups of the shorter one exit at once (workgroup-uniform,
 // before any barrier).  Measured against two launches of exactly sized grids: see cdetr_attn_bwd.
-template <int TB>
+template <int TB, bool LENS>
 __global__ __launch_bounds__(NTF) void bwd_kernel(const float* __restrict__ qg, long ldq, const float* __restrict__ kg, long ldk,
                                                   const float* __restrict__ vg, long ldv, const float* __restrict__ o,
                                                   const float* __restrict__ dO, const float* __restrict__ lse, float* __restrict__ dq,
-                                                  long lddq, float* __restrict__ dk, long lddk, float* __restrict__ dv, long lddv, int Lq,
-                                                  int Lk, int nh, float scale, int zbase) {
+                                                  long lddq, float* __restrict__ dk, long lddk, float* __restrict__ dv, long lddv, int Sq,
+                                                  int Sk, int nh, float scale, int zbase, const int32_t* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) __bf16 lds[2 * 4 * TILE];
     __shared__ __attribute__((aligned(16))) float stat[2][2][32];
     const int z = blockIdx.z + zbase;
-    if ((int)blockIdx.x * 32 * NWF >= (z == 0 ? Lq : Lk)) return;
-    if (z == 0) bwd_q_body<TB>(lds, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dq, lddq, Lq, Lk, nh, scale);
-    else bwd_kv_body<TB>(lds, stat, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dk, lddk, dv, lddv, Lq, Lk, nh, scale);
+    const int Lq = image_len<LENS>(lens, blockIdx.y / nh, Sq), Lk = LENS ? Lq : Sk;
+    if constexpr (LENS) {                          // padded rows of this workgroup's tile: exact zeros (the bodies store rows < len only)
+        const int n = blockIdx.y / nh, head = blockIdx.y % nh, lane = threadIdx.x & 63;
+        const int row = blockIdx.x * 32 * NWF + (threadIdx.x >> 6) * 32 + (lane & 31), g = lane >> 5;
+        if (z == 0 && row >= Lq && row < Sq) zero_own(dq + ((long)n * Sq + row) * lddq + head * D, g);
+        if (z != 0 && row >= Lk && row < Sk) {
+            zero_own(dk + ((long)n * Sk + row) * lddk + head * D, g);
+            zero_own(dv + ((long)n * Sk + row) * lddv + head * D, g);
+        }
+    }
+    if ((int)blockIdx.x * 32 * NWF >= (z == 0 ? Lq : Lk)) return;              // workgroup-uniform, before any barrier
+    if (z == 0) bwd_q_body<TB>(lds, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dq, lddq, Sq, Sk, Lq, Lk, nh, scale);
+    else bwd_kv_body<TB>(lds, stat, qg, ldq, kg, ldk, vg, ldv, o, dO, lse, dk, lddk, dv, lddv, Sq, Sk, Lq, Lk, nh, scale);
 }
 }  // namespace flash
 
@@ -732,37 +809,53 @@ struct Operands {
     float scale;
 };
 
-void launch_fwd(const Operands& a, float* o, float* lse, bool mfma, bool key_split, hipStream_t st) {
+template <bool LENS>
+void launch_fwd_t(const Operands& a, float* o, float* lse, bool mfma, bool key_split, const int32_t* lens, hipStream_t st) {
     const dim3 grid((a.Lq + 63) / 64, a.N * a.nh);
     if (mfma && key_split)
-        hipLaunchKernelGGL(flash::fwd_ks_kernel, grid, dim3(2 * flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+        hipLaunchKernelGGL(flash::fwd_ks_kernel<LENS>, grid, dim3(2 * flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh,
+                           a.scale, lens);
     else if (mfma)
-        hipLaunchKernelGGL(flash::fwd_kernel, grid, dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+        hipLaunchKernelGGL(flash::fwd_kernel<LENS>, grid, dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh,
+                           a.scale, lens);
     else
-        hipLaunchKernelGGL(mha_fwd_kernel, grid, dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale);
+        hipLaunchKernelGGL(mha_fwd_kernel<LENS>, grid, dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, lse, a.Lq, a.Lk, a.nh, a.scale, lens);
+}
+
+// lens (device, [N]; only with Lq == Lk): the per-image bound of cdetr_mha_*_lens; nullptr = the dense kernels
+void launch_fwd(const Operands& a, float* o, float* lse, bool mfma, bool key_split, hipStream_t st, const int32_t* lens = nullptr) {
+    if (lens) launch_fwd_t<true>(a, o, lse, mfma, key_split, lens, st);
+    else launch_fwd_t<false>(a, o, lse, mfma, key_split, nullptr, st);
 }
 
 // tb: 0 = the two fp32 VALU launches (D through `work`), 3 / 1 = one flash::bwd_kernel launch with split-bf16 / plain-bf16 gradient contractions
-void launch_bwd(const Operands& a, const float* o, const float* d_o, const float* lse, float* dq, long lddq, float* dk, long lddk, float* dv,
-                long lddv, float* work, int tb, bool two_launches, hipStream_t st) {
+template <bool LENS>
+void launch_bwd_t(const Operands& a, const float* o, const float* d_o, const float* lse, float* dq, long lddq, float* dk, long lddk, float* dv,
+                  long lddv, float* work, int tb, bool two_launches, const int32_t* lens, hipStream_t st) {
     const int gq = (a.Lq + 63) / 64, gk = (a.Lk + 63) / 64, nb = a.N * a.nh;
     if (tb == 0) {
-        hipLaunchKernelGGL(mha_bwd_q_kernel, dim3(gq, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, work,
-                           a.Lq, a.Lk, a.nh, a.scale);
-        hipLaunchKernelGGL(mha_bwd_kv_kernel, dim3(gk, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, d_o, lse, work, dk, lddk,
-                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale);
+        hipLaunchKernelGGL(mha_bwd_q_kernel<LENS>, dim3(gq, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, work,
+                           a.Lq, a.Lk, a.nh, a.scale, lens);
+        hipLaunchKernelGGL(mha_bwd_kv_kernel<LENS>, dim3(gk, nb), dim3(256), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, d_o, lse, work, dk, lddk,
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, lens);
         return;
     }
-    auto kern = (tb == 1) ? flash::bwd_kernel<1> : flash::bwd_kernel<3>;
+    auto kern = (tb == 1) ? flash::bwd_kernel<1, LENS> : flash::bwd_kernel<3, LENS>;
     if (two_launches) {
         hipLaunchKernelGGL(kern, dim3(gq, nb, 1), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, dk, lddk,
-                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0);
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0, lens);
         hipLaunchKernelGGL(kern, dim3(gk, nb, 1), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq, dk, lddk,
-                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 1);
+                           dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 1, lens);
     } else {
         hipLaunchKernelGGL(kern, dim3(max(gq, gk), nb, 2), dim3(flash::NTF), 0, st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, o, d_o, lse, dq, lddq,
-                           dk, lddk, dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0);
+                           dk, lddk, dv, lddv, a.Lq, a.Lk, a.nh, a.scale, 0, lens);
     }
+}
+
+void launch_bwd(const Operands& a, const float* o, const float* d_o, const float* lse, float* dq, long lddq, float* dk, long lddk, float* dv,
+                long lddv, float* work, int tb, bool two_launches, hipStream_t st, const int32_t* lens = nullptr) {
+    if (lens) launch_bwd_t<true>(a, o, d_o, lse, dq, lddq, dk, lddk, dv, lddv, work, tb, two_launches, lens, st);
+    else launch_bwd_t<false>(a, o, d_o, lse, dq, lddq, dk, lddk, dv, lddv, work, tb, two_launches, nullptr, st);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -790,6 +883,33 @@ extern "C" int cdetr_mha_bwd(const float* qk, const float* v, const float* o, co
     const int tb = precision == 3 ? 1 : precision == 1 ? 3 : 0;
     launch_bwd(a, o, d_o, lse, d_qk, 2 * E, d_qk + E, 2 * E, d_v, E, work, tb, false, reinterpret_cast<hipStream_t>(stream));
     return cdetr_launch_status("cdetr_mha_bwd");
+}
+
+// The ragged form: the same kernels (their LENS instantiations), the same kernel choice by L -- the host never sees the lengths.
+extern "C" int cdetr_mha_fwd_lens(const float* qk, const float* v, const int32_t* lens, float* o, float* lse, int32_t N, int32_t L, int32_t nh,
+                                  float scale, int32_t precision, void* stream) {
+    CDETR_CHECK_ARG(qk && v && lens && o && lse, "cdetr_mha_fwd_lens: null pointer");
+    CDETR_CHECK_ARG(N > 0 && L > 0 && nh > 0, "cdetr_mha_fwd_lens: bad sizes (N %d, L %d, nh %d)", N, L, nh);
+    CDETR_CHECK_ARG(aligned16(qk) && aligned16(v) && aligned16(o), "cdetr_mha_fwd_lens: operands must be 16-byte aligned");
+    const long E = (long)nh * D;
+    const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
+    const bool mfma = precision == 1;
+    launch_fwd(a, o, lse, mfma, mfma && L >= 128, reinterpret_cast<hipStream_t>(stream), lens);
+    return cdetr_launch_status("cdetr_mha_fwd_lens");
+}
+
+extern "C" int cdetr_mha_bwd_lens(const float* qk, const float* v, const int32_t* lens, const float* o, const float* d_o, const float* lse,
+                                  float* d_qk, float* d_v, float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision,
+                                  void* stream) {
+    CDETR_CHECK_ARG(qk && v && lens && o && d_o && lse && d_qk && d_v && work, "cdetr_mha_bwd_lens: null pointer");
+    CDETR_CHECK_ARG(N > 0 && L > 0 && nh > 0, "cdetr_mha_bwd_lens: bad sizes (N %d, L %d, nh %d)", N, L, nh);
+    CDETR_CHECK_ARG(aligned16(qk) && aligned16(v) && aligned16(o) && aligned16(d_o) && aligned16(d_qk) && aligned16(d_v),
+                    "cdetr_mha_bwd_lens: operands must be 16-byte aligned");
+    const long E = (long)nh * D;
+    const Operands a{qk, qk + E, v, 2 * E, 2 * E, E, N, L, L, nh, scale};
+    const int tb = precision == 3 ? 1 : precision == 1 ? 3 : 0;
+    launch_bwd(a, o, d_o, lse, d_qk, 2 * E, d_qk + E, 2 * E, d_v, E, work, tb, false, reinterpret_cast<hipStream_t>(stream), lens);
+    return cdetr_launch_status("cdetr_mha_bwd_lens");
 }
 
 // Forward kernel choice for the general problem: the key split (fwd_ks_kernel) from 128 keys on, as for cdetr_mha_fwd.  Measured at N = 2,

@@ -392,6 +392,74 @@ def _stage1_fields(samples):
     return out
 
 
+RAGGED_POINT_FILL = 0.5        # padded points sit in the image centre: finite through inverse_sigmoid and the sine embeddings
+
+
+def _stage1_ragged_fields(samples):
+    """_stage1_fields for samples with different numbers of points: points / whs padded to the batch maximum N with (0.5, 0.5) / 0 and
+    `counts` int32 [B] = each image's own number; rows n >= counts[b] of image b are padding."""
+    pts = [torch.as_tensor(s["points"], dtype=torch.float32).reshape(-1, 2) for s in samples]
+    counts = [p.shape[0] for p in pts]
+    if min(counts) == 0:
+        raise ValueError(f"collate_stage1_ragged: an image without points (counts {counts}); every image needs at least one")
+    B, N = len(samples), max(counts)
+    out = {"points": torch.full((B, N, 2), RAGGED_POINT_FILL, dtype=torch.float32), "counts": torch.tensor(counts, dtype=torch.int32),
+           "orig_size": torch.as_tensor(np.stack([np.asarray(s["orig_size"]) for s in samples]))}
+    for b, p in enumerate(pts):
+        out["points"][b, :counts[b]] = p
+    if "whs" in samples[0]:
+        out["whs"] = torch.zeros((B, N, 2), dtype=torch.float32)
+        for b, s in enumerate(samples):
+            out["whs"][b, :counts[b]] = torch.as_tensor(s["whs"], dtype=torch.float32).reshape(-1, 2)
+    if "im_id" in samples[0]:
+        out["im_id"] = torch.as_tensor([int(s["im_id"]) for s in samples])
+    return out
+
+
+def collate_stage1_ragged(samples):
+    """`collate_stage1` for images with different numbers of points: the same image / mask, points and whs padded to the batch maximum
+    (_stage1_ragged_fields) and `counts` [B] -- what Stage1Trainer.step(..., counts=) and stage1.write_pseudo_labels take."""
+    fields = _stage1_ragged_fields(samples)
+    image, mask = _pad_images(samples)
+    return {"image": image, "mask": mask, **fields}
+
+
+def collate_stage1_ragged_raw(samples):
+    """`collate_stage1_ragged` for raw=True samples (see collate_raw)."""
+    fields = _stage1_ragged_fields(samples)
+    return {"raw": pack_raw(samples), **fields}
+
+
+class SizeBucketBatchSampler(torch.utils.data.Sampler):
+    """Batches of dataset indices whose images share ONE resized size, for batched pseudo-label generation: a padded image changes
+    the key means (they run over padded rows and columns too, as in the reference's padded batches), so batches of one size keep the
+    batched labels equal to the batch-1 labels up to arithmetic noise.  The sizes come from the image headers (no decode) through the
+    dataset's own rule floor(w / sf) * sf; sizes in order of first appearance, dataset order within a size, the last batch of a size may
+    be short: the same batches on every pass."""
+
+    def __init__(self, dataset, batch_size):
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be at least 1, got {batch_size}")
+        sf = getattr(dataset, "scale_factor", 32)
+        buckets = {}
+        for idx, im_id in enumerate(dataset.data_split):
+            with Image.open(os.path.join(dataset.im_dir, im_id)) as im:
+                w, h = im.size
+            buckets.setdefault((sf * int(w / sf), sf * int(h / sf)), []).append(idx)
+        self.sizes = []
+        self.batches = []
+        for size, idxs in buckets.items():
+            for i in range(0, len(idxs), batch_size):
+                self.batches.append(idxs[i:i + batch_size])
+                self.sizes.append(size)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+    def __len__(self):
+        return len(self.batches)
+
+
 def build_dataset_stage1(args, image_set="train", raw=False):
     return FSC147ExemplarDataset(args, split=image_set, raw=raw)
 

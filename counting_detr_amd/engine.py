@@ -1563,7 +1563,9 @@ class Stage1Trainer(Trainer):
     stream-ordered `train_step` and the graph-captured `step` (linear graphs only, the chain layout).  Only the stage-specific hooks
     differ: the model call `model(samples, points)`, the fused BoundingBoxCriterion (ops.BBoxCriterionFn; no matcher, no loss
     normaliser to all-reduce), static buffers for (images, mask, points, whs), and captured steps keyed by (padded image shape,
-    points shape, arithmetic).  `transformer.cls_embed.*` is computed but never reaches the loss: its gradient is None in the
+    points shape, ragged or dense, arithmetic).  A ragged batch (`counts=`: images with different numbers of points, padded to the batch
+    maximum -- data.collate_stage1_ragged) keeps its counts in a static int32 buffer that the kernels read: batches of one padded shape
+    and any counts replay ONE captured graph.  `transformer.cls_embed.*` is computed but never reaches the loss: its gradient is None in the
     reference, so it stays out of the optimizer (as do the frozen stem and layer1).
     Out of scope: world_size > 1 (raises), --sgd (raises); the frozen-stage prefetch is off."""
 
@@ -1580,17 +1582,41 @@ class Stage1Trainer(Trainer):
         criterion.fused = True
         super().__init__(model, criterion, args, device=device, precision=precision, precision_bwd=precision_bwd)
         self._prefetch_on = False
+        self._counts = None                     # the counts tensor the model call of the running step / capture reads (ragged batches)
 
     @staticmethod
     def batch_args(ret):
         return ret["points"], ret["whs"]
 
     @staticmethod
-    def _targets(points, whs):
-        return {"points": points, "whs": whs}
+    def batch_kwargs(ret):
+        """Keyword arguments of `step` / `train_step` that a batch dict carries: the counts of a ragged batch."""
+        return {"counts": ret["counts"]} if ret.get("counts") is not None else {}
+
+    def _targets(self, points, whs, counts=None):
+        t = {"points": points, "whs": whs}
+        if counts is not None:
+            t["counts"] = self._check_counts(counts, points)
+        return t
+
+    def _check_counts(self, counts, points):
+        counts = torch.as_tensor(counts).to(device=self.device, dtype=torch.int32).contiguous()
+        if points.dim() != 3 or tuple(counts.shape) != (points.shape[0],):
+            raise ValueError(f"counts {tuple(counts.shape)} do not match points {tuple(points.shape)}: one count per image of [B,N,2]")
+        return counts
 
     def _call_model(self, images, mask, rects):
+        if self._counts is not None:
+            return self.model(NestedTensor(images, mask), rects, self._counts)
         return self.model(NestedTensor(images, mask), rects)
+
+    def _with_counts(self, targets, fn):
+        """Run fn() with the model call reading targets' counts (eager step) -- captures switch to their static buffer in _make_static."""
+        self._counts = targets.get("counts")
+        try:
+            return fn()
+        finally:
+            self._counts = None
 
     def _criterion_forward(self, outputs, targets, num_boxes):
         return self.criterion.forward_with_total(outputs, targets)
@@ -1605,7 +1631,7 @@ class Stage1Trainer(Trainer):
         return int(tmax)
 
     def _cache_key(self, images, rects, targets):
-        return (tuple(images.shape), tuple(rects.shape)) + self.arith
+        return (tuple(images.shape), tuple(rects.shape), "counts" in targets) + self.arith
 
     def _dry_run(self, st):
         with torch.no_grad():
@@ -1617,8 +1643,11 @@ class Stage1Trainer(Trainer):
         whs = targets["whs"].to(torch.float32).clone()
         if tuple(whs.shape) != tuple(pts.shape):
             raise ValueError(f"points {tuple(pts.shape)} and whs {tuple(whs.shape)} differ in shape")
-        return {"images": images.clone(), "mask": mask.clone(), "rects": pts, "whs": whs, "targets": self._targets(pts, whs),
-                "num_boxes": torch.ones(1, device=self.device, dtype=torch.float32), "sizes": tuple(pts.shape)}
+        counts = targets["counts"].clone() if "counts" in targets else None
+        self._counts = counts                   # the capture's model calls read the static buffer (cleared by the public entry point)
+        return {"images": images.clone(), "mask": mask.clone(), "rects": pts, "whs": whs, "counts": counts,
+                "targets": self._targets(pts, whs, counts), "num_boxes": torch.ones(1, device=self.device, dtype=torch.float32),
+                "sizes": tuple(pts.shape)}
 
     def _load_entry(self, e, images, mask, rects, targets):
         st = e["st"]
@@ -1626,6 +1655,10 @@ class Stage1Trainer(Trainer):
                 or tuple(targets["whs"].shape) != tuple(st["whs"].shape):
             raise ValueError(f"captured step holds images {tuple(st['images'].shape)} / points {tuple(st['rects'].shape)}, "
                              f"got {tuple(images.shape)} / {tuple(rects.shape)} / whs {tuple(targets['whs'].shape)}")
+        if (st["counts"] is None) != ("counts" not in targets):
+            raise ValueError("a step captured with counts replays batches with counts, one captured without them dense batches")
+        if st["counts"] is not None:
+            st["counts"].copy_(targets["counts"])
         st["images"].copy_(images)
         st["mask"].copy_(mask)
         st["rects"].copy_(rects)
@@ -1633,22 +1666,26 @@ class Stage1Trainer(Trainer):
         e["loads"] += 1
 
     # public entry points: (samples, points [B,N,2], whs [B,N,2]) instead of (samples, rects, targets)
-    def train_step(self, samples, points, whs):
+    def train_step(self, samples, points, whs, *, counts=None):
         """Eager (stream-ordered) step.  samples: [B,3,H,W] tensor, list of [3,h,w] tensors, or NestedTensor; points / whs [B,N,2]
-        normalised (exemplar centres and sizes).  Returns device scalars {loss_wh, loss_giou, loss, grad_norm}."""
-        return Trainer.train_step(self, samples, points, self._targets(points, whs))
+        normalised (exemplar centres and sizes); counts [B]: a ragged batch, image b's rows beyond counts[b] are padding.
+        Returns device scalars {loss_wh, loss_giou, loss, grad_norm}."""
+        t = self._targets(points, whs, counts)
+        return self._with_counts(t, lambda: Trainer.train_step(self, samples, points, t))
 
-    def step(self, samples, points, whs, next_samples=None):
-        """One step at graph-replay speed: captured steps are cached by (padded image shape, points shape, arithmetic); a batch of a
-        cached key is copied into the static buffers and replayed.  Returns the loss dict (device scalars, valid until the same entry
-        is replayed again)."""
-        return Trainer.step(self, samples, points, self._targets(points, whs))
+    def step(self, samples, points, whs, next_samples=None, *, counts=None):
+        """One step at graph-replay speed: captured steps are cached by (padded image shape, points shape, ragged or dense,
+        arithmetic); a batch of a cached key is copied into the static buffers -- its counts too -- and replayed.  Returns the loss dict
+        (device scalars, valid until the same entry is replayed again)."""
+        t = self._targets(points, whs, counts)
+        return self._with_counts(t, lambda: Trainer.step(self, samples, points, t))
 
-    def capture(self, samples, points, whs, warmup=0):
-        return Trainer.capture(self, samples, points, self._targets(points, whs), warmup)
+    def capture(self, samples, points, whs, warmup=0, *, counts=None):
+        t = self._targets(points, whs, counts)
+        return self._with_counts(t, lambda: Trainer.capture(self, samples, points, t, warmup))
 
-    def replay(self, samples=None, points=None, whs=None):
-        return Trainer.replay(self, samples, points, None if whs is None else self._targets(points, whs))
+    def replay(self, samples=None, points=None, whs=None, *, counts=None):
+        return Trainer.replay(self, samples, points, None if whs is None else self._targets(points, whs, counts))
 
 
 def train_one_epoch(trainer, data_loader, epoch, print_freq=100, log=print):
@@ -1687,7 +1724,8 @@ def train_one_epoch(trainer, data_loader, epoch, print_freq=100, log=print):
         nxt_img = nxt["image"] if (nxt is not None and torch.is_tensor(nxt.get("image"))) else None
         # cached HIP graph per padded size / target-capacity class; the next batch's image tensor is announced (frozen-stage prefetch)
         batch_args = getattr(trainer, "batch_args", Trainer.batch_args)
-        out = trainer.step(samples, *batch_args(ret), next_samples=nxt_img)
+        batch_kwargs = getattr(trainer, "batch_kwargs", None)           # (Stage1Trainer: the counts of a ragged batch)
+        out = trainer.step(samples, *batch_args(ret), next_samples=nxt_img, **(batch_kwargs(ret) if batch_kwargs else {}))
         if keys is None:
             keys = sorted(k for k, v in out.items() if torch.is_tensor(v))
             acc = torch.zeros(len(keys), device=trainer.device, dtype=torch.float32)

@@ -1248,22 +1248,39 @@ def rcda_core(q_row, q_col, k_row, k_col, v, mask_row, mask_col, nh):
 
 
 # ----------------------------------------------------------------------------------------------------- decoder self-attention
-def mha_fwd_raw(qk, v, nh):
+def _check_lens(lens, N, device):
+    """lens / counts of a ragged batch: an int32 DEVICE tensor [N] that the kernels read (never a host list baked into a launch)."""
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (N,) or lens.device != device or not lens.is_contiguous():
+        raise ValueError(f"lens must be a contiguous int32 tensor [{N}] on {device}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+    return lens
+
+
+def mha_fwd_raw(qk, v, nh, lens=None):
+    """lens [N] int32 (device): image n's first lens[n] rows attend to each other, rows beyond come back as exact zeros
+    (cdetr_mha_fwd_lens); None = every row (cdetr_mha_fwd)."""
     N, L, E2 = qk.shape
     E = E2 // 2
     o = torch.empty((N, L, E), device=qk.device, dtype=torch.float32)
     lse = torch.empty((N, nh, L), device=qk.device, dtype=torch.float32)
+    if lens is not None:
+        check(lib().cdetr_mha_fwd_lens(ptr(qk), ptr(v), ptr(_check_lens(lens, N, qk.device)), ptr(o), ptr(lse), N, L, nh, (E // nh) ** -0.5,
+                                       PRECISION, stream_ptr()), "cdetr_mha_fwd_lens")
+        return o, lse
     check(lib().cdetr_mha_fwd(ptr(qk), ptr(v), ptr(o), ptr(lse), N, L, nh, (E // nh) ** -0.5, PRECISION, stream_ptr()), "cdetr_mha_fwd")
     return o, lse
 
 
-def mha_bwd_raw(qk, v, o, d_o, lse, nh):
+def mha_bwd_raw(qk, v, o, d_o, lse, nh, lens=None):
     N, L, E2 = qk.shape
     E = E2 // 2
     d_qk = torch.empty_like(qk)
     d_v = torch.empty_like(v)
     work = torch.empty((N, nh, L), device=qk.device, dtype=torch.float32)
     prec = bwd_precision() if MHA_BWD_BF16 else PRECISION      # 3: split-bf16 scores, plain-bf16 gradient contractions (A/B: CDETR_MHA_BWD_BF16=0)
+    if lens is not None:
+        check(lib().cdetr_mha_bwd_lens(ptr(qk), ptr(v), ptr(_check_lens(lens, N, qk.device)), ptr(o), ptr(d_o), ptr(lse), ptr(d_qk), ptr(d_v),
+                                       ptr(work), N, L, nh, (E // nh) ** -0.5, prec, stream_ptr()), "cdetr_mha_bwd_lens")
+        return d_qk, d_v
     check(lib().cdetr_mha_bwd(ptr(qk), ptr(v), ptr(o), ptr(d_o), ptr(lse), ptr(d_qk), ptr(d_v), ptr(work), N, L, nh,
                               (E // nh) ** -0.5, prec, stream_ptr()), "cdetr_mha_bwd")
     return d_qk, d_v
@@ -1273,23 +1290,24 @@ class MhaCoreFn(torch.autograd.Function):
     """softmax(q k^T / sqrt(d)) v per head for the decoder queries (qk [N,L,2E] = q | k, v [N,L,E]) in one fused kernel."""
 
     @staticmethod
-    def forward(ctx, qk, v, nh):
+    def forward(ctx, qk, v, nh, lens=None):
         assert qk.shape[-1] == 2 * nh * 32, "the MHA kernels are specialised for head_dim 32"
         qk, v = qk.contiguous(), v.contiguous()
-        o, lse = mha_fwd_raw(qk, v, nh)
+        o, lse = mha_fwd_raw(qk, v, nh, lens)
         ctx.save_for_backward(qk, v, o, lse)
-        ctx.nh = nh
+        ctx.nh, ctx.lens = nh, lens
         return o
 
     @staticmethod
     def backward(ctx, d_o):
         qk, v, o, lse = ctx.saved_tensors
-        d_qk, d_v = mha_bwd_raw(qk, v, o, d_o.contiguous(), lse, ctx.nh)
-        return d_qk, d_v, None
+        d_qk, d_v = mha_bwd_raw(qk, v, o, d_o.contiguous(), lse, ctx.nh, ctx.lens)
+        return d_qk, d_v, None, None
 
 
-def mha_core(qk, v, nh):
-    return MhaCoreFn.apply(qk, v, nh)
+def mha_core(qk, v, nh, lens=None):
+    """lens: per-image valid query counts of a ragged batch (int32 device tensor [N]); see mha_fwd_raw."""
+    return MhaCoreFn.apply(qk, v, nh, lens)
 
 
 # ----------------------------------------------------------------------------------------------------- general attention core
@@ -1713,11 +1731,15 @@ class DecoderStackFn(torch.autograd.Function):
     autograd never runs an accumulation kernel for them."""
 
     @staticmethod
-    def forward(ctx, tgt, qpos, qx, qy, memory, krm, kcm, mask_row, mask_col, layers, anchor, posemb_row=None, posemb_col=None):
+    def forward(ctx, tgt, qpos, qx, qy, memory, krm, kcm, mask_row, mask_col, layers, anchor, posemb_row=None, posemb_col=None, lens=None):
         """krm / kcm: the key means mean_H(memory) + posemb_row, mean_W(memory) + posemb_col -- or None with posemb_row / posemb_col
         given: then they are formed here (one launch) and their backward folds into the memory gradient (one launch) instead of
-        four tensor launches each way."""
+        four tensor launches each way.
+        lens (int32 device tensor [N], or None): image n's queries beyond lens[n] are padding -- keys of nobody's self-attention in
+        every layer, forward and backward (the only place where the queries of one image meet); everywhere else they are rows like
+        any other, finite and unused."""
         N, L, E = tgt.shape
+        ctx.lens = lens
         _, H, W, _ = memory.shape
         M = N * L
         tgt, qpos, qx, qy = tgt.contiguous(), qpos.contiguous(), qx.contiguous(), qy.contiguous()
@@ -1752,7 +1774,7 @@ class DecoderStackFn(torch.autograd.Function):
             with gemm_queue():
                 qk = linear_fwd(a1, Ws[0:2 * E], bs[0:2 * E])
                 vs = linear_fwd(x, Ws[2 * E:3 * E], bs[2 * E:3 * E])
-            o1, lse = mha_fwd_raw(qk.view(N, L, 2 * E), vs.view(N, L, E), nh)
+            o1, lse = mha_fwd_raw(qk.view(N, L, 2 * E), vs.view(N, L, E), nh, lens)
             Y2 = linear_fwd(o1.view(M, E), sa.out_proj.weight.detach(), sa.out_proj.bias.detach(), resid=x)
             T1, mu2, rs2, qr_in, qc_in = ln_fwd_add_raw(Y2, layer.norm2.weight.detach(), layer.norm2.bias.detach(), layer.norm2.eps,
                                                         qx.view(M, E), qy.view(M, E))
@@ -1844,7 +1866,7 @@ class DecoderStackFn(torch.autograd.Function):
                              merge=(gx, gy, acc_x, acc_y))
             _wg(dY2, o1.view(M, E), sa.out_proj.weight, sa.out_proj.bias, 0, E)
             dO1 = linear_dgrad(dY2, sa.out_proj.weight.detach()).view(N, L, E)
-            dqk, dvs = mha_bwd_raw(qk.view(N, L, 2 * E), vs.view(N, L, E), o1, dO1, lse, sa.num_heads)
+            dqk, dvs = mha_bwd_raw(qk.view(N, L, 2 * E), vs.view(N, L, E), o1, dO1, lse, sa.num_heads, ctx.lens)
             Wsp, bsp = sa.in_proj_weight, sa.in_proj_bias
             _wg(dqk.view(M, 2 * E), a1, Wsp, bsp, 0, 2 * E)
             _wg(dvs.view(M, E), x, Wsp, bsp, 2 * E, 3 * E)
@@ -1856,9 +1878,9 @@ class DecoderStackFn(torch.autograd.Function):
         if ctx.own_means:        # memory also fed the two key means: broadcast their gradients back in the same pass
             dMem = bcast_add2(dMem.view(N, H, W, E), dKrm, dKcm, 1.0 / H, 1.0 / W)
             return (dx.view(N, L, E), acc_p.view(N, L, E), acc_x.view(N, L, E), acc_y.view(N, L, E), dMem, None, None, None, None, None,
-                    None, dKrm.view(N, W, E), dKcm.view(N, H, E))
+                    None, dKrm.view(N, W, E), dKcm.view(N, H, E), None)
         return (dx.view(N, L, E), acc_p.view(N, L, E), acc_x.view(N, L, E), acc_y.view(N, L, E), dMem.view(N, H, W, E),
-                dKrm.view(N, W, E), dKcm.view(N, H, E), None, None, None, None, None, None)
+                dKrm.view(N, W, E), dKcm.view(N, H, E), None, None, None, None, None, None, None)
 
 
 # ----------------------------------------------------------------------------------------------------- matcher
@@ -2178,10 +2200,12 @@ class BBoxCriterionFn(torch.autograd.Function):
     vec = [loss_wh, loss_giou, w_wh * loss_wh + w_giou * loss_giou].  `coord` is the box head's [B,N,4] output (cxcywh); its wh
     columns are read in place (pointer + row stride, no copy) and its xy columns take no part (stage 1 builds both boxes around the
     GIVEN points).  tgt_points / tgt_whs [B,N,2].  The forward leaves the gradient of both losses w.r.t. pred_wh; backward is one
-    scaled sum (cdetr_bbox_criterion_bwd) into d_coord [B,N,4] with zeros in the xy columns."""
+    scaled sum (cdetr_bbox_criterion_bwd) into d_coord [B,N,4] with zeros in the xy columns.
+    counts (int32 device tensor [B], or None): the valid pairs of a ragged batch are rows n < counts[b]; the sums and the normaliser
+    M = sum(counts) are formed by the kernel from device memory (cdetr_bbox_criterion_lens_*), padded rows get zero gradients."""
 
     @staticmethod
-    def forward(ctx, coord, tgt_points, tgt_whs, w_wh, w_giou):
+    def forward(ctx, coord, tgt_points, tgt_whs, w_wh, w_giou, counts=None):
         if coord.dim() != 3 or coord.shape[-1] != 4 or coord.dtype != torch.float32:
             raise ValueError(f"BBoxCriterionFn: coord must be float32 [B,N,4], got {tuple(coord.shape)} {coord.dtype}")
         B, N, _ = coord.shape
@@ -2198,8 +2222,14 @@ class BBoxCriterionFn(torch.autograd.Function):
         losses = torch.empty(3, device=dev, dtype=torch.float32)
         g = torch.empty(4 * M, device=dev, dtype=torch.float32)
         g_wh, g_giou = g[:2 * M], g[2 * M:]
-        check(lib().cdetr_bbox_criterion_fwd(ptr(coord) + 8, coord.stride(1), ptr(tp), ptr(tw), M, float(w_wh), float(w_giou),
-                                             ptr(losses), ptr(g_wh), ptr(g_giou), stream_ptr()), "cdetr_bbox_criterion_fwd")
+        ctx.counts = counts
+        if counts is not None:
+            check(lib().cdetr_bbox_criterion_lens_fwd(ptr(coord) + 8, coord.stride(1), ptr(tp), ptr(tw), ptr(_check_lens(counts, B, dev)), B, N,
+                                                      float(w_wh), float(w_giou), ptr(losses), ptr(g_wh), ptr(g_giou), stream_ptr()),
+                  "cdetr_bbox_criterion_lens_fwd")
+        else:
+            check(lib().cdetr_bbox_criterion_fwd(ptr(coord) + 8, coord.stride(1), ptr(tp), ptr(tw), M, float(w_wh), float(w_giou),
+                                                 ptr(losses), ptr(g_wh), ptr(g_giou), stream_ptr()), "cdetr_bbox_criterion_fwd")
         ctx.g, ctx.dims, ctx.w = (g_wh, g_giou), (B, N), (float(w_wh), float(w_giou))
         return losses
 
@@ -2208,9 +2238,13 @@ class BBoxCriterionFn(torch.autograd.Function):
         B, N = ctx.dims
         g_wh, g_giou = ctx.g
         d_coord = torch.empty((B, N, 4), device=g_wh.device, dtype=torch.float32)
+        if ctx.counts is not None:
+            check(lib().cdetr_bbox_criterion_lens_bwd(ptr(g3.contiguous()), ctx.w[0], ctx.w[1], ptr(g_wh), ptr(g_giou), ptr(ctx.counts),
+                                                      ptr(d_coord), B, N, stream_ptr()), "cdetr_bbox_criterion_lens_bwd")
+            return d_coord, None, None, None, None, None
         check(lib().cdetr_bbox_criterion_bwd(ptr(g3.contiguous()), ctx.w[0], ctx.w[1], ptr(g_wh), ptr(g_giou), ptr(d_coord), B * N,
                                              stream_ptr()), "cdetr_bbox_criterion_bwd")
-        return d_coord, None, None, None, None
+        return d_coord, None, None, None, None, None
 
 
 class SineEmbedFn(torch.autograd.Function):

@@ -173,13 +173,14 @@ class MultiheadSelfAttention(nn.Module):
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.constant_(self.out_proj.bias, 0.0)
 
-    def forward(self, qk_in, v_in, resid=None):
-        """qk_in, v_in: [N,L,E] batch-first.  Returns out_proj(attn) (+ resid) [N,L,E]."""
+    def forward(self, qk_in, v_in, resid=None, lens=None):
+        """qk_in, v_in: [N,L,E] batch-first.  Returns out_proj(attn) (+ resid) [N,L,E].  lens (int32 device tensor [N]): image n's
+        rows beyond lens[n] are padding, keys of nobody (ops.mha_core)."""
         N, L, E = qk_in.shape
         nh, d = self.num_heads, E // self.num_heads
         qk = ops.linear(qk_in, self.in_proj_weight, self.in_proj_bias, rows=(0, 2 * E))        # q and k in one GEMM
         v = ops.linear(v_in, self.in_proj_weight, self.in_proj_bias, rows=(2 * E, 3 * E))
-        o = ops.mha_core(qk, v, nh)                       # fused scale / QK^T / softmax / PV kernel
+        o = ops.mha_core(qk, v, nh, lens)                 # fused scale / QK^T / softmax / PV kernel
         return self.out_proj(o, resid=resid)
 
 
@@ -266,8 +267,8 @@ class TransformerDecoderLayer(nn.Module):
         self.norm2 = LayerNorm(d_model)
         self.ffn = FFN(d_model, d_ffn)
 
-    def forward(self, tgt, query_pos, query_pos_x, query_pos_y, memory, k_row_mean, k_col_mean, mask_row, mask_col):
-        tgt = self.norm2(self.self_attn(tgt + query_pos, tgt, resid=tgt))                        # :369-372
+    def forward(self, tgt, query_pos, query_pos_x, query_pos_y, memory, k_row_mean, k_col_mean, mask_row, mask_col, lens=None):
+        tgt = self.norm2(self.self_attn(tgt + query_pos, tgt, resid=tgt, lens=lens))             # :369-372
         a = self.cross_attn.attend(tgt + query_pos_x, tgt + query_pos_y, k_row_mean, k_col_mean, memory,
                                    mask_row, mask_col, resid=tgt)                                # :385-403
         tgt = self.norm1(a)
@@ -382,11 +383,21 @@ class Transformer(nn.Module):
             return pts.unsqueeze(0).repeat(bs, self.num_pattern, 1)
         raise ValueError(f"unknown {self.spatial_prior} spatial prior")
 
-    def forward(self, src, mask, points=None):
+    def forward(self, src, mask, points=None, counts=None):
         """src: NHWC [B,h,w,C] (the product path keeps NHWC); mask: bool [B,h,w] or the ops.MaskInfo the model derived from the
         image-level padding mask.  Returns (([classes [B,Q,ncls]] , [coords [B,Q,4]], [vars [B,Q,2]]) -- one entry per decoder layer
-        whose heads are evaluated (all with aux losses, else the last) --, reference_points [B,Q,2])."""
+        whose heads are evaluated (all with aux losses, else the last) --, reference_points [B,Q,2]).
+        counts (int32 device tensor [B], stage 1's ragged batches): image b's points beyond counts[b] are padding; its first
+        counts[b] queries come out as `points[b, :counts[b]]` alone would give them, the others finite and meaningless."""
         bs, h, w, c = src.shape
+        if counts is not None:
+            if self.spatial_prior != "defined":
+                raise ValueError(f"counts belong to spatial_prior 'defined' (the queries ARE the given points), not {self.spatial_prior!r}")
+            if self.num_pattern != 1:
+                raise ValueError(f"counts need num_query_pattern == 1 (query n <-> point n), got {self.num_pattern}")
+            if self.attention_type != "RCDA" or not src.is_cuda:
+                raise NotImplementedError("counts are implemented for attention_type 'RCDA' on the device")
+            counts = ops._check_lens(counts, bs, src.device)
         mi = mask if isinstance(mask, ops.MaskInfo) else ops.mask_prep(mask, h, w)
         reference_points = self.reference_points(bs, src.device, points)
         pattern = self.pattern if self.stage == 2 else self.modify_pattern
@@ -428,7 +439,7 @@ class Transformer(nn.Module):
         last = len(self.decoder_layers) - 1
         if self.fused_decoder and src.is_cuda:
             args = (tgt, query_pos, query_pos_x, query_pos_y, memory, None, None, mask_row, mask_col, list(self.decoder_layers),
-                    pattern.weight, posemb_row, posemb_col)
+                    pattern.weight, posemb_row, posemb_col, counts)
             if grad:
                 layer_outs = ops.DecoderStackFn.apply(*args)
             else:
@@ -439,7 +450,7 @@ class Transformer(nn.Module):
             k_col_mean = memory.mean(2) + posemb_col
             layer_outs, output = [], tgt
             for layer in self.decoder_layers:
-                output = layer(output, query_pos, query_pos_x, query_pos_y, memory, k_row_mean, k_col_mean, mask_row, mask_col)
+                output = layer(output, query_pos, query_pos_x, query_pos_y, memory, k_row_mean, k_col_mean, mask_row, mask_col, lens=counts)
                 layer_outs.append(output)
         return self._heads(layer_outs, reference_points)
 

@@ -369,6 +369,16 @@ int cdetr_mha_fwd(const float* qk, const float* v, float* o, float* lse, int32_t
 int cdetr_mha_bwd(const float* qk, const float* v, const float* o, const float* d_o, const float* lse, float* d_qk, float* d_v,
                   float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision, void* stream);
 
+/* The ragged form (stage-1 batches whose images carry different numbers of queries).  Layout and arithmetic are cdetr_mha_fwd / _bwd's; image
+ * n still starts at row n*L, and lens [N] (int32, DEVICE memory, read by the kernels -- a captured graph follows new lengths) gives the masking
+ * bound len = clamp(lens[n], 0, L) on the query AND the key side: rows >= len are no one's keys, their qk / v / d_o values are never read into a
+ * valid row (select, not multiplication: NaN there is harmless).  Written for rows >= len: o, lse, d_qk, d_v = exact 0.  lens[n] == 0 gives an
+ * all-zero image.  With every lens[n] == L the results are cdetr_mha_fwd / _bwd's bit for bit.  Pointers 16-byte aligned.                    */
+int cdetr_mha_fwd_lens(const float* qk, const float* v, const int32_t* lens, float* o, float* lse, int32_t N, int32_t L, int32_t nh,
+                       float scale, int32_t precision, void* stream);
+int cdetr_mha_bwd_lens(const float* qk, const float* v, const int32_t* lens, const float* o, const float* d_o, const float* lse, float* d_qk,
+                       float* d_v, float* work, int32_t N, int32_t L, int32_t nh, float scale, int32_t precision, void* stream);
+
 /* ---- general attention core (nn.MultiheadAttention(256, 8) without masks: the encoder self-attention over all h*w tokens and the
  * decoder cross-attention from Q queries to h*w keys of attention_type "nn.MultiheadAttention", A2/models/transformer.py:262-272,393-398)
  * o = softmax(scale * q k^T) v per head, head dim 32, E = nh*32.  q: N images of Lq rows, row stride ldq (image n starts at row n*Lq);
@@ -464,6 +474,16 @@ int cdetr_bbox_criterion_fwd(const float* pred_wh, int64_t pred_stride, const fl
                              float w_wh, float w_giou, float* losses, float* g_wh, float* g_giou, void* stream);
 int cdetr_bbox_criterion_bwd(const float* g3, float w_wh, float w_giou, const float* g_wh, const float* g_giou, float* d_coord,
                              int32_t M, void* stream);
+
+/* The ragged form: B images of N rows, lens [B] (int32, DEVICE memory); row n of image b is a pair iff n < clamp(lens[b], 0, N).  The sums run
+ * over the valid pairs and the normaliser M = sum(lens) is formed in the kernel.  Padded rows of pred_wh / tgt_* are never read; their g_wh /
+ * g_giou / d_coord rows are exact zeros.  M == 0 gives losses and gradients of 0.  One workgroup, ordered reductions; with every lens[b] == N
+ * the losses and gradients are cdetr_bbox_criterion_fwd / _bwd's (M = B*N) bit for bit.                                                      */
+int cdetr_bbox_criterion_lens_fwd(const float* pred_wh, int64_t pred_stride, const float* tgt_points, const float* tgt_whs,
+                                  const int32_t* lens, int32_t B, int32_t N, float w_wh, float w_giou, float* losses, float* g_wh,
+                                  float* g_giou, void* stream);
+int cdetr_bbox_criterion_lens_bwd(const float* g3, float w_wh, float w_giou, const float* g_wh, const float* g_giou, const int32_t* lens,
+                                  float* d_coord, int32_t B, int32_t N, void* stream);
 
 /* ---- box-AP evaluation (csrc/coco_eval.hip): pycocotools' COCOeval, bbox path, as restated in counting_detr_amd/coco_ap.py -- what the
  * reference's offline evaluator runs on the host (A2/eval_all.py:285-312, 496-531).  All values FLOAT64, finite; contraction into FMAs is

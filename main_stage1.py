@@ -9,8 +9,12 @@ and every 10 epochs), one JSON line per epoch in log.txt.
   --generate_pseudo_label  load --resume and write pseudo_bbox_{train,val,test}.json (the 2nd stage's training labels), then exit
   --auto_resume            continue from <output_dir>/checkpoint.pth: weights, AdamW moments, StepLR state and the next epoch
   --synthetic              seeded batches, no dataset
-Differences: any number of images per step with equal exemplar counts (--batch_size; the reference trains batch 1), and the step runs
-as cached HIP graphs (--no_graph_cache: stream-ordered).  --sgd and multi-GPU training are not supported.
+  --ragged_batches         batches may mix images with different numbers of points (padded to the batch maximum, per-image counts read by
+                           the kernels): training with any --batch_size on a real split, --eval likewise, and --generate_pseudo_label
+                           runs --batch_size images of one resized size per forward
+Differences: any number of images per step (--batch_size; the reference trains batch 1) -- with equal exemplar counts, or any counts
+with --ragged_batches -- and the step runs as cached HIP graphs (--no_graph_cache: stream-ordered).  --sgd and multi-GPU training are
+not supported.
 
   python main_stage1.py --data_path ./FSC147/ --output_dir ./outputs/fscd_147_1st_stage --resume ./pretrained_models/AnchorDETR_r50_c5.pth
   python main_stage1.py --data_path ./FSC147/ --output_dir ./outputs/fscd_147_1st_stage --dataset_file fscd_147_point \\
@@ -59,9 +63,17 @@ def loader_for(args, split, points=False, shuffle=False, device=None):
     from torch.utils.data import DataLoader
     from counting_detr_amd import data
     raw = bool(getattr(args, "device_preprocess", False))
+    ragged = bool(getattr(args, "ragged_batches", False))
     ds = data.build_points_dataset(args, split, raw=raw) if points else data.build_dataset_stage1(args, split, raw=raw)
-    dl = DataLoader(ds, batch_size=1 if points else args.batch_size, shuffle=shuffle,
-                    collate_fn=data.collate_stage1_raw if raw else data.collate_stage1, num_workers=args.num_workers, drop_last=shuffle)
+    if ragged:
+        collate_fn = data.collate_stage1_ragged_raw if raw else data.collate_stage1_ragged
+    else:
+        collate_fn = data.collate_stage1_raw if raw else data.collate_stage1
+    if points and ragged:                      # pseudo labels: --batch_size images of ONE resized size per forward, in a fixed order
+        dl = DataLoader(ds, batch_sampler=data.SizeBucketBatchSampler(ds, args.batch_size), collate_fn=collate_fn, num_workers=args.num_workers)
+    else:
+        dl = DataLoader(ds, batch_size=1 if points else args.batch_size, shuffle=shuffle, collate_fn=collate_fn, num_workers=args.num_workers,
+                        drop_last=shuffle)
     return data.Prefetcher(dl, device) if raw else dl
 
 
@@ -72,8 +84,12 @@ def evaluate(model, criterion, loader, device):
     model.eval()
     acc, n = None, 0
     for ret in to_device(loader, device):
-        out = model(NestedTensor(ret["image"], ret["mask"]), ret["points"])
-        ld, total = criterion.forward_with_total(out, {"points": ret["points"], "whs": ret["whs"]})
+        counts = ret.get("counts")             # --ragged_batches: the model and the criterion see each image's own points only
+        out = model(NestedTensor(ret["image"], ret["mask"]), ret["points"], counts)
+        targets = {"points": ret["points"], "whs": ret["whs"]}
+        if counts is not None:
+            targets["counts"] = counts
+        ld, total = criterion.forward_with_total(out, targets)
         v = torch.stack([total, ld["loss_wh"], ld["loss_giou"]])
         acc = v if acc is None else acc + v
         n += 1
