@@ -236,6 +236,73 @@ class SetCriterion(nn.Module):
             self.last_total = totals[0] if len(totals) == 1 else torch.stack(totals).sum()
         return losses
 
+    @torch.no_grad()
+    def per_image(self, outputs, targets, indices=None, out=None):
+        """The losses EVERY image of the batch would get evaluated alone -- what the reference's inference driver logs (A2/infer.py:27-122
+        runs one image per call): a dict with the keys of `forward`, each a [B] tensor; entry b normalises by max(T_b, 1), takes the
+        variance means over image b's own pairs and the cardinality error of image b.  `forward` on the batch gives other numbers (one
+        normaliser and one variance mean for the whole batch, the cardinality error averaged over the images).
+        On the device: ONE batched `match_device` call as in `forward` (with `aux_outputs`: the layers matched as there), then one
+        cdetr_criterion_eval launch per layer (ops.criterion_eval; no gradients, no host sync); `self.last_rows` keeps the last layer's
+        [B, 7] rows (the six scalars in the kernel's order + the weighted total), written into `out` when given, and `self.last_match` the
+        matcher's (idx_i, idx_j, plan).  On CPU tensors: the tensor-op composition (`loss_labels` ...) applied image by image -- the checker;
+        there is no host assignment solver in the package, so `indices` = [(idx_i, idx_j) of image b, ...] (a list of such lists, one per
+        layer, with `aux_outputs`) must be given.  On the device `indices` is not used."""
+        last_out = {k: v for k, v in outputs.items() if k not in ("aux_outputs", "enc_outputs")}
+        layers = list(outputs.get("aux_outputs") or []) + [last_out]
+        L = len(layers)
+        logits = last_out["pred_logits"]
+        B, Q = logits.shape[:2]
+        per_layer = []
+        if logits.is_cuda:
+            if list(self.losses) != ["labels", "boxes", "cardinality", "vars"]:
+                raise RuntimeError(f"per_image: cdetr_criterion_eval computes [labels, boxes, cardinality, vars], not {list(self.losses)}")
+            plan, tgt_boxes, tgt_labels, packed = self._targets_of(targets, Q, logits.device)
+            if L > 1 and packed:              # capacity plan: one match per layer with the one device-resident plan, as in `forward`
+                per = [self.matcher.match_device(lo, None, plan, tgt_boxes=tgt_boxes) for lo in layers]
+                idx_i, idx_j, status = (torch.cat([r[k] for r in per]) for k in range(3))
+            elif L > 1:
+                plan_all = self._plan(tuple(plan.sizes) * L, Q, logits.device)
+                stacked = {k: torch.cat([lo[k] for lo in layers]) for k in ("pred_logits", "pred_boxes")}
+                idx_i, idx_j, status, _ = self.matcher.match_device(stacked, None, plan_all, tgt_boxes=tgt_boxes.repeat(L, 1))
+            else:
+                idx_i, idx_j, status, _ = self.matcher.match_device(last_out, None, plan, tgt_boxes=tgt_boxes)
+            if self.check_status and bool((status != 0).any()):
+                raise ValueError("invalid or infeasible matching cost matrix")
+            self.last_match = (idx_i, idx_j, plan)
+            tgt_labels = tgt_labels.to(torch.int64)
+            for li, lo in enumerate(layers):
+                last = li == L - 1
+                rows = ops.criterion_eval(lo["pred_logits"].float(), lo["pred_boxes"].float(), lo["pred_vars"].float(), tgt_boxes, tgt_labels, plan,
+                                          idx_i[li * B:(li + 1) * B], idx_j[li * B:(li + 1) * B], self.num_classes, self.focal_alpha,
+                                          self._weights6(logits.device, None if last else li), out=out if last else None)
+                per_layer.append({k: rows[:, c] for c, k in enumerate(("loss_ce", "class_error", "cardinality_error", "loss_bbox", "loss_giou",
+                                                                       "loss_variance"))})
+            self.last_rows = rows
+        else:
+            if indices is None:
+                raise RuntimeError("per_image: CPU tensors need `indices` (the package has no host assignment solver; the device path matches itself)")
+            if L == 1 and (len(indices) == 0 or torch.is_tensor(indices[0][0])):
+                indices = [indices]
+            for lo, ind in zip(layers, indices):
+                rows = []
+                for b in range(B):
+                    one = {k: lo[k][b:b + 1] for k in ("pred_logits", "pred_boxes", "pred_vars")}
+                    tb, tl = targets[b]["boxes"].to(torch.float32).reshape(-1, 4), targets[b]["labels"].reshape(-1)
+                    plan = ops.MatchPlan((tb.shape[0],), Q, logits.device)
+                    ii, jj = (torch.as_tensor(x, dtype=torch.int64).reshape(1, -1) for x in ind[b])
+                    bidx, sidx, tidx = self._matched(ii, jj, plan)
+                    d = {}
+                    for loss in self.losses:
+                        d.update(getattr(self, "loss_" + loss)(one, plan, bidx, sidx, tidx, tb, tl, max(float(tb.shape[0]), 1.0)))
+                    rows.append(d)
+                per_layer.append({k: torch.stack([r[k].reshape(()) for r in rows]) for k in rows[0]})
+        losses = {}                                 # `forward`'s order: the aux layers first (class_error is logged for the last layer only), then the last
+        for li, d in enumerate(per_layer[:-1]):
+            losses.update({k + f"_{li}": v for k, v in d.items() if k != "class_error"})
+        losses.update(per_layer[-1])
+        return losses
+
     def _weights6(self, device, layer):
         """weight_dict entries of one layer's six scalars, in the fused kernel's order (0 for the logged-only ones), on the device."""
         key = (str(device), layer)

@@ -62,6 +62,9 @@ def get_args_parser():
                    help="infer.py / main.py --eval: threshold, scaling, truncation and COCOeval's ordering of the detections on the device "
                         "(cdetr_emit_detections, one call per image, one copy back per split); the same predictions json byte for byte, the box "
                         "AP matched from device memory without re-reading it (--ap_on_host: ap_from_json on the written file)")
+    p.add_argument("--eval_batch_size", default=1, type=int,
+                   help="infer.py / main.py --eval: images per forward.  1: the reference's loop.  More: batches of images of ONE resized size "
+                        "(bucket order), the logged losses stay per-image quantities (SetCriterion.per_image, one cdetr_criterion_eval launch per batch)")
     # additions of this build (the reference hard-codes batch 1 on one GPU)
     p.add_argument("--dataset", default="fsc147", choices=["fsc147", "fscd_lvis"], help="reader used without --synthetic")
     p.add_argument("--images_per_gpu", default=2, type=int, help="local batch of the data-parallel trainer")

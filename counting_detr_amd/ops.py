@@ -2195,6 +2195,44 @@ class CriterionFn(torch.autograd.Function):
         return (d_logits, d_boxes, d_vars) + (None,) * 9
 
 
+def criterion_eval(logits, boxes, pvars, tgt_boxes, tgt_labels, plan, idx_i, idx_j, num_classes, alpha, w6=None, out=None, events=None):
+    """cdetr_criterion_eval: SetCriterion's six scalars + the weighted total for EVERY image of a batch as if it were evaluated alone, forward
+    only, in one launch (one workgroup per image) -> losses fp32 [B, 7]: row b = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou,
+    loss_variance, sum_k w6[k] row[k] (0 without `w6`)] with the normaliser max(T_b, 1) and the variance means over image b's own pairs.
+    Arguments as ops.CriterionFn (device tensors; `plan` a MatchPlan, exact or capacity: the counts are read from its device table); no
+    autograd.  out: a contiguous fp32 [B, 7] tensor to write into (a row range of a split-wide buffer).  events: a pair of torch.cuda.Event
+    recorded right before / after the launch (tools/eval_batch_time.py)."""
+    from ._ffi import CriterionEvalDesc
+    B, Q, Cc = logits.shape
+    if plan.B != B or plan.Q != Q or tuple(idx_i.shape) != (B, plan.Mmax) or tuple(idx_j.shape) != (B, plan.Mmax):
+        raise RuntimeError(f"criterion_eval: logits [{B}, {Q}, {Cc}] with a plan of B = {plan.B}, Q = {plan.Q}, Mmax = {plan.Mmax} and indices "
+                           f"{tuple(idx_i.shape)}, {tuple(idx_j.shape)}")
+    logits, boxes, pvars = logits.detach().contiguous(), boxes.detach().contiguous(), pvars.detach().contiguous()
+    for name, t, dt_ in (("logits", logits, torch.float32), ("boxes", boxes, torch.float32), ("vars", pvars, torch.float32),
+                         ("tgt_boxes", tgt_boxes, torch.float32), ("tgt_labels", tgt_labels, torch.int64), ("idx_i", idx_i, torch.int64),
+                         ("idx_j", idx_j, torch.int64)):
+        if t.dtype != dt_ or not t.is_contiguous():
+            raise RuntimeError(f"criterion_eval: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    if tuple(boxes.shape) != (B, Q, 4) or tuple(pvars.shape) != (B, Q, 2):
+        raise RuntimeError(f"criterion_eval: boxes [B, Q, 4] and vars [B, Q, 2] expected, got {tuple(boxes.shape)}, {tuple(pvars.shape)}")
+    if out is None:
+        out = torch.empty((B, 7), device=logits.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 7) or not out.is_contiguous() or out.device != logits.device:
+        raise RuntimeError(f"criterion_eval: `out` must be a contiguous fp32 [{B}, 7] tensor on {logits.device}")
+    d = CriterionEvalDesc()
+    d.B, d.Q, d.C, d.num_classes, d.Mmax, d.alpha = B, Q, Cc, num_classes, plan.Mmax, alpha
+    d.logits, d.boxes, d.vars = ptr(logits), ptr(boxes), ptr(pvars)
+    d.tgt_boxes = ptr(tgt_boxes) if tgt_boxes.numel() else ptr(out)             # never read without targets
+    d.tgt_labels = ptr(tgt_labels) if tgt_labels.numel() else ptr(out)
+    d.tgt_off, d.idx_i, d.idx_j, d.losses, d.loss_weights = ptr(plan.tgt_off), ptr(idx_i), ptr(idx_j), ptr(out), ptr(w6)
+    if events is not None:
+        events[0].record()
+    check(lib().cdetr_criterion_eval(C.byref(d), stream_ptr()), "cdetr_criterion_eval")
+    if events is not None:
+        events[1].record()
+    return out
+
+
 class BBoxCriterionFn(torch.autograd.Function):
     """The 1st-stage BoundingBoxCriterion (A1/models/anchor_detr.py:317-337) in one launch (cdetr_bbox_criterion_fwd): returns
     vec = [loss_wh, loss_giou, w_wh * loss_wh + w_giou * loss_giou].  `coord` is the box head's [B,N,4] output (cxcywh); its wh

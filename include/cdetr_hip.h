@@ -460,6 +460,31 @@ int cdetr_criterion_bwd(const float* g6, const float* g_total, const float* loss
                         const float* g_giou, const float* g_var_box, const float* g_vars, float* d_logits, float* d_boxes, float* d_vars,
                         int32_t BQ, int32_t C, void* stream);
 
+/* cdetr_criterion_eval (csrc/criterion_eval.hip): the evaluation form -- forward only, one workgroup per image (grid = B, no limit of 64 and
+ * none on B*Q; LDS holds one image's Q target classes).  Row b of losses [B][7] is what SetCriterion returns for image b evaluated ALONE, as
+ * the reference's inference driver does (A2/infer.py:27-122): the normaliser is max(T_b, 1), formed in the kernel from tgt_off (no num_boxes,
+ * no all-reduce); cardinality_error = |#object queries of image b - T_b|; the means of loss_variance run over image b's own min(Q, T_b)
+ * pairs; without pairs class_error = 100 and loss_bbox = loss_giou = loss_variance = 0; a negative variance gives NaN in its own row only.
+ * Same order of the six scalars and same expressions as cdetr_criterion_fwd; losses[b][6] = sum_k loss_weights[k] * losses[b][k] (0 when
+ * loss_weights is NULL).  Inputs as in cdetr_criterion_desc; the counts are read from device memory, so a capacity plan and a captured
+ * graph serve any target counts.  Ordered reductions (wave tree, then a serial sum over the waves): bit-reproducible, and row b does not
+ * depend on the other images of the batch.                                                                                            */
+typedef struct {
+    int32_t B, Q, C, num_classes, Mmax;
+    float alpha;
+    const float* logits;        /* [B,Q,C] */
+    const float* boxes;         /* [B,Q,4] cxcywh */
+    const float* vars;          /* [B,Q,2] */
+    const float* tgt_boxes;     /* [sum T,4] */
+    const int64_t* tgt_labels;  /* [sum T] */
+    const int32_t* tgt_off;     /* [B+1] */
+    const int64_t* idx_i;       /* [B,Mmax] */
+    const int64_t* idx_j;       /* [B,Mmax] */
+    float* losses;              /* [B,7] */
+    const float* loss_weights;  /* optional [6] (NULL = absent) */
+} cdetr_criterion_eval_desc;
+int cdetr_criterion_eval(const cdetr_criterion_eval_desc* d, void* stream);
+
 /* ---- 1st-stage BoundingBoxCriterion (A1/models/anchor_detr.py:317-337; no matcher: query n of image b <-> exemplar n) --------------
  * cdetr_bbox_criterion_fwd: M = B*N pairs, src = [tgt_points, pred_wh], tgt = [tgt_points, tgt_whs] (cxcywh):
  *   losses[3] = { loss_wh = mean |pred_wh - tgt_whs| (2M elements), loss_giou = sum (1 - GIoU(src, tgt)) / M,

@@ -14,8 +14,15 @@ cdetr_emit_detections call per image appends its wire records (the json's fields
 a device-resident store, the losses go to a device buffer, and nothing is copied or awaited inside the loop; after it, one copy of the store
 writes the SAME predictions json byte for byte and the AP is matched from device memory without re-reading that file.
 
+`--eval_batch_size B` (default 1: the loop above, one image per forward): the split is walked in batches of B images of ONE resized size
+(data.SizeBucketBatchSampler: a padded image is not the image alone -- the key means run over padded cells), in bucket order.  The logged
+losses stay what they are at batch 1, per-image quantities averaged over the split: `SetCriterion.per_image` gives every image the losses it
+would get alone (one batched match + one cdetr_criterion_eval launch per batch), where the batched `forward` would normalise by the batch's
+target count.  The json lists the images in the order they were run; AP and the counting metrics do not depend on it.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --eval_batch_size 16
 """
 import json
 import os
@@ -30,11 +37,14 @@ from counting_detr_amd.misc import NestedTensor
 
 
 @torch.no_grad()
-def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None):
+def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
+          per_image=False):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
-    (the split's instances json) the metrics also carry the box AP, matched from the device-resident detections."""
+    (the split's instances json) the metrics also carry the box AP, matched from the device-resident detections.
+    `per_image` (--eval_batch_size > 1): the loader yields batches of several images of one size; the losses are `criterion.per_image`'s, one
+    value per image, summed image by image -- what the batch-1 loop logs."""
     output_path = os.path.join(output_dir, "predictions_" + split + ".json")
     if os.path.isfile(output_path):
         os.remove(output_path)
@@ -43,7 +53,7 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     from counting_detr_amd.engine import InferenceEngine
     engine = InferenceEngine(model, threshold, graphs=graphs and torch.device(device).type == "cuda", device=device)
     if device_detections:
-        return _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json)
+        return _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image)
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
     pred_counts, gt_counts, loss_sum, n_img = [], [], {}, 0
@@ -63,9 +73,14 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         rects = ret["ex_rects"].to(device)
         targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
         _, keep, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects, next_samples=next_image)      # forward + :75-81
-        loss_dict = criterion(outputs, targets)
-        for k, v in loss_dict.items():
-            loss_sum[k] = loss_sum.get(k, 0.0) + float(v) * len(targets)
+        if per_image:
+            for k, v in criterion.per_image(outputs, targets).items():
+                for x in v.tolist():                # float(v[b]) in image order
+                    loss_sum[k] = loss_sum.get(k, 0.0) + x
+        else:
+            loss_dict = criterion(outputs, targets)
+            for k, v in loss_dict.items():
+                loss_sum[k] = loss_sum.get(k, 0.0) + float(v) * len(targets)
         for b in range(image.shape[0]):
             ori_h, ori_w = [int(x) for x in ret["orig_size"][b]]
             image_id = int(ret["image_id"][b]) if "image_id" in ret else n_img
@@ -104,8 +119,9 @@ def _num_images(data_loader):
     raise RuntimeError("infer: device_detections needs the number of images up front (a DataLoader, a data.Prefetcher or a list of batches)")
 
 
-def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json):
-    """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer, one
+def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False):
+    """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
+    cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
     and image ids into a device table.  After the loop: one copy each of the store, the table and the loss buffer; the json is written from the
     store's arrays (same bytes as the host loop's file), the losses are summed in Python in the same order (same floats), the counts are the
@@ -124,7 +140,7 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             rects = ret["ex_rects"].to(device)
             targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
             _, _, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects)
-            loss_dict = criterion(outputs, targets)
+            loss_dict = criterion.per_image(outputs, targets) if per_image else criterion(outputs, targets)
             B, Q = prob.shape
             if store is None:
                 store = ops.DetectionStore(N, Q, device, threshold=threshold, max_det=MAX_DETS)
@@ -133,7 +149,14 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
                 loss_buf = torch.zeros((N, len(loss_keys)), dtype=torch.float64, device=device)      # fp32 -> fp64 is exact: float(v) of the host loop
             if n_img + B > N or list(loss_dict) != loss_keys:
                 raise RuntimeError(f"infer: the loader yields more than its {N} images, or the criterion changed its losses")
-            loss_buf[n_batch].copy_(torch.stack([v.detach().reshape(()).to(torch.float64) for v in loss_dict.values()]))
+            if not per_image:
+                loss_buf[n_batch].copy_(torch.stack([v.detach().reshape(()).to(torch.float64) for v in loss_dict.values()]))
+                n_targets.append(len(targets))
+                n_batch += 1
+            else:
+                loss_buf[n_batch:n_batch + B].copy_(torch.stack(list(loss_dict.values()), 1))      # [B, keys]: the kernel's rows, one per image
+                n_targets += [1] * B
+                n_batch += B
             rows = meta[n_img:n_img + B]
             rows[:, :2].copy_(torch.as_tensor(ret["orig_size"]).reshape(B, 2), non_blocking=True)
             if "image_id" in ret:
@@ -141,10 +164,8 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             else:
                 rows[:, 2].copy_(torch.arange(n_img, n_img + B))
             store.emit(prob.contiguous(), outputs["pred_boxes"].contiguous(), ref_points.reshape(B, Q, 2).contiguous(), rows[:, :2].to(torch.int32))
-            n_targets.append(len(targets))
             gt_counts += [int(t["boxes"].shape[0]) for t in targets]
             n_img += B
-            n_batch += 1
         predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
         loss_sum, pred_counts, image_ids = {}, [], []
         if n_img:
@@ -186,6 +207,25 @@ def counting_metrics_from_json(pred_json, gt_json, threshold=0.5):
     return counting_metrics([cnt[i] for i in ids], [len(gt.getAnnIds([i])) for i in ids])
 
 
+def eval_loader(args, device):
+    """-> (loader of the evaluation split, per_image).  --eval_batch_size 1 (the default): one image per batch in dataset order, batched losses
+    (the reference's loop).  B > 1: batches of up to B images of one resized size in bucket order (data.SizeBucketBatchSampler), per-image losses."""
+    from torch.utils.data import DataLoader
+    raw = bool(getattr(args, "device_preprocess", False))               # workers decode only; resize + normalise + pad on the device
+    ds = data.build_test_dataset(args, image_set=args.split, raw=raw)
+    collate_fn = data.collate_raw if raw else data.collate
+    B = int(getattr(args, "eval_batch_size", 1))
+    if B < 1:
+        raise ValueError(f"--eval_batch_size must be at least 1, got {B}")
+    if B > 1:
+        dl = DataLoader(ds, batch_sampler=data.SizeBucketBatchSampler(ds, B), collate_fn=collate_fn, num_workers=args.num_workers)
+    else:
+        dl = DataLoader(ds, batch_size=1, shuffle=False, collate_fn=collate_fn, num_workers=args.num_workers)
+    if raw:
+        dl = data.Prefetcher(dl, device)
+    return dl, B > 1
+
+
 def main(args):
     device = torch.device(args.device)
     model, criterion, _ = counting_detr_amd.build_model(args)
@@ -193,18 +233,13 @@ def main(args):
     if args.resume:
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(ckpt["model"], strict=True)
-    from torch.utils.data import DataLoader
-    raw = bool(getattr(args, "device_preprocess", False))               # workers decode only; resize + normalise + pad on the device
-    ds = data.build_test_dataset(args, image_set=args.split, raw=raw)
-    dl = DataLoader(ds, batch_size=1, shuffle=False, collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers)
-    if raw:
-        dl = data.Prefetcher(dl, device)
+    dl, per_image = eval_loader(args, device)
     os.makedirs(args.output_dir, exist_ok=True)
     gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
     on_device = bool(getattr(args, "device_detections", False))
     ap_in_loop = on_device and os.path.isfile(gt_json) and not getattr(args, "ap_on_host", False)      # matched from the device-resident detections
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
-                       gt_json=gt_json if ap_in_loop else None)
+                       gt_json=gt_json if ap_in_loop else None, per_image=per_image)
     if os.path.isfile(gt_json) and not ap_in_loop:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers

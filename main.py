@@ -122,17 +122,11 @@ def main(args):
     if args.eval and not args.synthetic:                                # counting evaluation on the validation split (A2/infer.py)
         if utils.is_main_process():
             import infer as _infer
-            from torch.utils.data import DataLoader
-            from counting_detr_amd import data
-            raw = bool(getattr(args, "device_preprocess", False))
-            dl = DataLoader(data.build_test_dataset(args, image_set=args.split, raw=raw), batch_size=1, shuffle=False,
-                            collate_fn=data.collate_raw if raw else data.collate, num_workers=args.num_workers)
-            if raw:
-                dl = data.Prefetcher(dl, device)
+            dl, per_image = _infer.eval_loader(args, device)           # --eval_batch_size: batches of one resized size, per-image losses
             on_device = bool(getattr(args, "device_detections", False))      # post-forward work + box AP on the device (infer.py)
             gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
             metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
-                                      gt_json=gt_json if on_device and os.path.isfile(gt_json) else None)
+                                      gt_json=gt_json if on_device and os.path.isfile(gt_json) else None, per_image=per_image)
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
