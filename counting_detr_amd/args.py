@@ -163,6 +163,16 @@ def get_args_parser_stage1():
     p.add_argument("--device_preprocess", action="store_true",
                    help="the DataLoader workers only decode; resize (PIL-exact), normalisation and padding run on the device in one launch per "
                         "batch (cdetr_image_prep) -- the same image / mask tensors bit for bit")
+    p.add_argument("--test", action="store_true",
+                   help="for val and test: forward at the centres of the ground-truth boxes of instances_<split>.json and score every predicted "
+                        "box against its own ground truth (mean IoU, share of IoU >= 0.5 / 0.75) and as detections (box AP): "
+                        "box_scores_<split>.json, then exit")
+    p.add_argument("--score_labels", action="store_true",
+                   help="with --generate_pseudo_label: box AP of pseudo_bbox_{val,test}.json against instances_<split>.json "
+                        "(the offline evaluator's conventions): pseudo_scores_<split>.json")
+    p.add_argument("--device_labels", action="store_true",
+                   help="with --generate_pseudo_label or --test: the labels leave the forward on the device (cdetr_emit_pseudo_labels, one call "
+                        "per batch, one copy back per split); the same json byte for byte, the scores read from device memory")
     return p
 
 

@@ -336,6 +336,10 @@ class FSC147PointsDataset(Dataset):
     def __len__(self):
         return len(self.data_split)
 
+    def point_counts(self):
+        """Annotated dots per image, in dataset order, without opening an image (sizes stage1's device label store)."""
+        return [len(self.annotations[im_id]["points"]) for im_id in self.data_split]
+
     def __getitem__(self, idx):
         im_id = self.data_split[idx]
         anno = self.annotations[im_id]
@@ -349,6 +353,46 @@ class FSC147PointsDataset(Dataset):
         return {"im_id": int(im_id[:-4]), **image, "points": all_points / res[None, :],
                 "labels": np.zeros(all_points.shape[0], dtype=np.int64), "anchor_points": centres / res[None, :],
                 "orig_size": np.array([img_w, img_h])}
+
+
+class FSC147BoxPointsDataset(Dataset):
+    """The 1st-stage view of a split that has box ground truth (A1/datasets/fscd_147.py:150-242, FSCD147_Test, with the split's own
+    `instances_<split>.json`): the fields of FSC147PointsDataset with `points` = the centres of the ground-truth boxes (normalised by the
+    original size with FSC147EvalDataset's arithmetic), plus `gt_xywh` float64 [P,4] = the json's [x1, y1, w, h] untouched and `image_id` =
+    the json's image id -- what main_stage1.py --test forwards and pairs the predicted sizes with."""
+
+    def __init__(self, args, split="val", raw=False):
+        data_path = args.data_path
+        self.raw = raw
+        self.im_dir = os.path.join(data_path, "images_384_VarV2")
+        self.scale_factor = getattr(args, "scale_factor", 32)
+        self.annotations = _load_json(os.path.join(data_path, "annotation_FSC147_384.json"))
+        self.data_split = _load_json(os.path.join(data_path, "Train_Test_Val_FSC_147.json"))[split]
+        self.label = CocoIndex(os.path.join(data_path, f"instances_{split}.json"))
+        self.name2id = {v["file_name"]: v["id"] for v in self.label.imgs.values()}
+
+    def __len__(self):
+        return len(self.data_split)
+
+    def point_counts(self):
+        """Ground-truth boxes per image, in dataset order, without opening an image (sizes stage1's device label store)."""
+        return [len(self.label.getAnnIds([self.name2id[name]])) for name in self.data_split]
+
+    def __getitem__(self, idx):
+        name = self.data_split[idx]
+        image_id = self.name2id[name]
+        annos = self.label.loadAnns(self.label.getAnnIds([image_id]))
+        centers = np.array([[a["bbox"][0] + a["bbox"][2] / 2, a["bbox"][1] + a["bbox"][3] / 2] for a in annos], dtype=np.float32).reshape(-1, 2)
+        gt_xywh = np.array([a["bbox"] for a in annos], dtype=np.float64).reshape(-1, 4)
+        anchors, _ = _exemplar_centres_whs(self.annotations[name])
+        image = Image.open(os.path.join(self.im_dir, name))
+        img_w, img_h = image.size
+        res4 = np.array([img_w, img_h, img_w, img_h], dtype=np.float32)
+        sf = self.scale_factor
+        image = _image_fields(image, (sf * int(img_w / sf), sf * int(img_h / sf)), Image.BILINEAR, self.raw)
+        return {"im_id": int(name[:-4]), "image_id": image_id, **image, "points": centers / res4[None, :2],
+                "labels": np.zeros(centers.shape[0], dtype=np.int64), "anchor_points": anchors / res4[None, :2],
+                "orig_size": np.array([img_w, img_h]), "gt_xywh": gt_xywh}
 
 
 def collate_stage1(samples):
@@ -389,6 +433,9 @@ def _stage1_fields(samples):
         out["whs"] = torch.stack([torch.as_tensor(s["whs"], dtype=torch.float32).reshape(-1, 2) for s in samples])
     if "im_id" in samples[0]:
         out["im_id"] = torch.as_tensor([int(s["im_id"]) for s in samples])
+    if "gt_xywh" in samples[0]:                # FSC147BoxPointsDataset
+        out["gt_xywh"] = torch.stack([torch.as_tensor(s["gt_xywh"], dtype=torch.float64).reshape(-1, 4) for s in samples])
+        out["image_id"] = torch.as_tensor([int(s["image_id"]) for s in samples])
     return out
 
 
@@ -413,6 +460,11 @@ def _stage1_ragged_fields(samples):
             out["whs"][b, :counts[b]] = torch.as_tensor(s["whs"], dtype=torch.float32).reshape(-1, 2)
     if "im_id" in samples[0]:
         out["im_id"] = torch.as_tensor([int(s["im_id"]) for s in samples])
+    if "gt_xywh" in samples[0]:                # FSC147BoxPointsDataset: the ground-truth boxes, padded with zeros like whs
+        out["gt_xywh"] = torch.zeros((B, N, 4), dtype=torch.float64)
+        for b, s in enumerate(samples):
+            out["gt_xywh"][b, :counts[b]] = torch.as_tensor(s["gt_xywh"], dtype=torch.float64).reshape(-1, 4)
+        out["image_id"] = torch.as_tensor([int(s["image_id"]) for s in samples])
     return out
 
 
@@ -466,6 +518,10 @@ def build_dataset_stage1(args, image_set="train", raw=False):
 
 def build_points_dataset(args, image_set="train", raw=False):
     return FSC147PointsDataset(args, split=image_set, raw=raw)
+
+
+def build_box_points_dataset(args, image_set="val", raw=False):
+    return FSC147BoxPointsDataset(args, split=image_set, raw=raw)
 
 
 def build_dataset(args, raw=False):

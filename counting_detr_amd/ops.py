@@ -2146,6 +2146,101 @@ class DetectionStore:
         return self._host
 
 
+def emit_pseudo_labels(points, pred_wh, counts, orig_wh, store, first, gt_xywh=None, events=None):
+    """cdetr_emit_pseudo_labels: append the stage-1 pseudo labels of one forwarded batch to `store` (a PseudoLabelStore) as its images
+    first .. first + B - 1.  Device tensors: points fp32 [B, R, 2] normalised, pred_wh fp32 [B, R, 2], counts int32 [B] (None: every row of a
+    dense batch), orig_wh int32 [B, 2] = (width, height), gt_xywh float64 [B, R, 4] (None: no paired IoU).  One launch on the current
+    stream, nothing comes back to the host; a record range that does not fit the store sets its status word (PseudoLabelStore.finish
+    raises).  events: a pair of torch.cuda.Event recorded right before / after the call."""
+    from ._ffi import EmitPseudoLabelsDesc
+    for name, t, dt_ in (("points", points, torch.float32), ("pred_wh", pred_wh, torch.float32), ("counts", counts, torch.int32),
+                         ("orig_wh", orig_wh, torch.int32), ("gt_xywh", gt_xywh, torch.float64)):
+        if t is not None and (t.dtype != dt_ or not t.is_contiguous()):
+            raise RuntimeError(f"emit_pseudo_labels: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    if points.dim() != 3 or points.shape[2] != 2 or tuple(pred_wh.shape) != tuple(points.shape) or tuple(orig_wh.shape) != (points.shape[0], 2) \
+            or (counts is not None and tuple(counts.shape) != (points.shape[0],)) \
+            or (gt_xywh is not None and tuple(gt_xywh.shape) != tuple(points.shape[:2]) + (4,)):
+        raise RuntimeError(f"emit_pseudo_labels: points [B, R, 2], pred_wh [B, R, 2], counts [B], orig_wh [B, 2], gt_xywh [B, R, 4] expected, got "
+                           f"{tuple(points.shape)}, {tuple(pred_wh.shape)}, {None if counts is None else tuple(counts.shape)}, {tuple(orig_wh.shape)}, "
+                           f"{None if gt_xywh is None else tuple(gt_xywh.shape)}")
+    for name, t in (("pred_wh", pred_wh), ("counts", counts), ("orig_wh", orig_wh), ("gt_xywh", gt_xywh)):
+        if t is not None and t.device != points.device:
+            raise RuntimeError(f"emit_pseudo_labels: `{name}` on {t.device}, points on {points.device}")
+    if points.device != store.buf.device:
+        raise RuntimeError(f"emit_pseudo_labels: a batch on {points.device} into a store on {store.buf.device}")
+    B, R = points.shape[:2]
+    d = EmitPseudoLabelsDesc()
+    d.B, d.R, d.N, d.first, d.max_det, d.row_cap, d.eval_cap = B, R, store.N, int(first), store.max_det, store.row_cap, store.eval_cap
+    d.points, d.pred_wh, d.counts, d.orig_wh, d.gt_xywh = ptr(points), ptr(pred_wh), ptr(counts), ptr(orig_wh), ptr(gt_xywh)
+    d.img_counts, d.row_off, d.eval_off, d.status = ptr(store.counts), ptr(store.row_off), ptr(store.eval_off), ptr(store.status)
+    d.wire, d.pair_iou = ptr(store.wire), ptr(store.pair_iou)
+    d.eval_boxes, d.eval_area, d.eval_score = ptr(store.eval_boxes), ptr(store.eval_area), ptr(store.eval_score)
+    if events is not None:
+        events[0].record()
+    check(lib().cdetr_emit_pseudo_labels(C.byref(d), stream_ptr()), "cdetr_emit_pseudo_labels")
+    if events is not None:
+        events[1].record()
+
+
+class PseudoLabelStore:
+    """The stage-1 pseudo labels of a whole split on the device, filled batch by batch by cdetr_emit_pseudo_labels (`emit`) and read back ONCE
+    (`finish`).  One byte buffer: [status | counts [N] | row_off [N + 1] | eval_off [N + 1] | eval_score f64 [eval_cap] | wire int32 [row_cap, 8]
+    | pair_iou f64 [row_cap]] is what `finish` copies; [eval_boxes f64 [eval_cap, 4] | eval_area f64 [eval_cap]] behind it never leaves the
+    device (coco_ap.summarize_store hands them to cdetr_coco_match: the store carries the members coco_ap.pack_store reads of a
+    DetectionStore).  row_cap = the rows (annotated dots) of the split; at most min(row_cap, N * max_det) of them become evaluation records."""
+
+    def __init__(self, n_images, row_cap, device, max_det=1100):
+        self.N, self.row_cap, self.max_det = int(n_images), int(row_cap), int(max_det)
+        if self.N < 1 or self.row_cap < 0 or self.max_det < 0:
+            raise RuntimeError(f"PseudoLabelStore: bad sizes N = {self.N}, row_cap = {self.row_cap}, max_det = {self.max_det}")
+        self.eval_cap = min(self.row_cap, self.N * self.max_det)
+        if self.row_cap > 1 << 30:
+            raise RuntimeError(f"PseudoLabelStore: {self.row_cap} records exceed the 2^30 of cdetr_emit_pseudo_labels")
+        al = lambda n: (n + 15) // 16 * 16                                                                     # noqa: E731
+        N, cuts = self.N, [0]
+        for nbytes in (16, 4 * N, 4 * (N + 1), 4 * (N + 1), 8 * self.eval_cap, 32 * self.row_cap, 8 * self.row_cap, 32 * self.eval_cap,
+                       8 * self.eval_cap):
+            cuts.append(cuts[-1] + al(nbytes))
+        self.buf = torch.empty(cuts[-1], dtype=torch.uint8, device=device)
+        self.buf[:cuts[4]].zero_()                                                                             # status, counts, row_off[0], eval_off[0]
+        part = lambda k, dt_, n: self.buf[cuts[k]:cuts[k + 1]].view(dt_)[:n]                                   # noqa: E731
+        self.status, self.counts = part(0, torch.int32, 1), part(1, torch.int32, N)
+        self.row_off, self.eval_off = part(2, torch.int32, N + 1), part(3, torch.int32, N + 1)
+        self.eval_score, self.wire = part(4, torch.float64, self.eval_cap), part(5, torch.int32, 8 * self.row_cap).view(-1, 8)
+        self.pair_iou = part(6, torch.float64, self.row_cap)
+        self.eval_boxes, self.eval_area = part(7, torch.float64, 4 * self.eval_cap).view(-1, 4), part(8, torch.float64, self.eval_cap)
+        self._cuts, self.first, self._host = cuts, 0, None
+
+    def emit(self, points, pred_wh, counts, orig_wh, gt_xywh=None, events=None):
+        """Append one forwarded batch (see emit_pseudo_labels); returns the store index of its first image."""
+        first, B = self.first, points.shape[0]
+        if first + B > self.N:
+            raise RuntimeError(f"PseudoLabelStore: image {first + B} into a store of {self.N}")
+        emit_pseudo_labels(points, pred_wh, counts, orig_wh, self, first, gt_xywh=gt_xywh, events=events)
+        self.first, self._host = first + B, None
+        return first
+
+    def finish(self):
+        """ONE device -> host copy (it waits for the emits): dict of numpy arrays for the n images emitted so far -- counts [n], row_off /
+        eval_off [n + 1], wire int32 [W, 6] (store image index, cx, cy, w, h, area), pair_iou f64 [W], eval_score f64 [E].  Raises if a
+        record range did not fit the store."""
+        if self._host is None:
+            c, n = self._cuts, self.first
+            h = self.buf[:c[7]].cpu().numpy()
+            status = int(h[:4].view("int32")[0])
+            if status:
+                raise RuntimeError(f"PseudoLabelStore: cdetr_emit_pseudo_labels reported status {status} (1: more than {self.row_cap} wire records, "
+                                   f"2: more than {self.eval_cap} evaluation records, 4: inconsistent offsets, 8: a count outside the batch's rows); "
+                                   "the images concerned were not written")
+            i32 = lambda k, m: h[c[k]:c[k] + 4 * m].view("int32")                                              # noqa: E731
+            row_off, eval_off = i32(2, n + 1), i32(3, n + 1)
+            W, E = int(row_off[n]), int(eval_off[n])
+            self._host = {"counts": i32(1, n), "row_off": row_off, "eval_off": eval_off,
+                          "wire": h[c[5]:c[5] + 32 * W].view("int32").reshape(W, 8)[:, :6], "pair_iou": h[c[6]:c[6] + 8 * W].view("float64"),
+                          "eval_score": h[c[4]:c[4] + 8 * E].view("float64")}
+        return self._host
+
+
 class CriterionFn(torch.autograd.Function):
     """SetCriterion's six scalars in one launch (cdetr_criterion_fwd); returns (vec, total) with
     vec = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou, loss_variance] and total = sum_k w6[k] vec[k] (the weighted

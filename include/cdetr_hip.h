@@ -627,6 +627,54 @@ typedef struct {
 } cdetr_emit_detections_desc;
 int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream);
 
+/* ---- stage-1 pseudo labels emitted on the device (csrc/stage1_labels.hip): what the 1st stage's label writer does per annotated dot on the
+ * host between the forward and pseudo_bbox_<split>.json (A1/engine.py:124-187; stage1.write_pseudo_labels' loop), plus the offline
+ * evaluator's reading of that file (A1/offline_coco_evaluator.py:134-143: [cx, cy, w, h] -> a detection [cx - w/2, cy - h/2, w, h] of score
+ * 1.0) and the IoU of every pseudo box with the ground-truth box its dot is the centre of, EQUAL to the host path (the loop,
+ * stage1.score_pseudo_labels, coco_ap.box_iou_xywh); FMA contraction is switched off in this translation unit.
+ * cdetr_emit_pseudo_labels: ONE launch per forwarded batch on `stream` (workgroups of 256 rows x B images), appending the batch's images
+ *   first .. first + B - 1 to a device-resident STORE that holds a whole split of N images:
+ *     img_counts [N]   rows per image (counts[b], or R for a dense batch);
+ *     row_off [N + 1] / eval_off [N + 1]: image n owns wire records and paired IoUs row_off[n] .. row_off[n + 1] and evaluation records
+ *                      eval_off[n] .. eval_off[n + 1].  The call READS entry `first` (written by the previous call in stream order; entry 0 is
+ *                      zeroed by the caller once) and writes entries first + 1 .. first + B as running sums of this batch's own counts.
+ *                      Placement is deterministic: no atomic decides where a record lands.
+ *     wire [row_cap][8] int32, ROW order: with W = (float)ori_w, H = (float)ori_h and xf = px * W, yf = py * H, wf = pw * W, hf = ph * H
+ *                      (one fp32 multiply each): { store image index n, trunc(xf), trunc(yf), trunc(wf), trunc(hf), trunc(wf * hf) (fp32
+ *                      product of the unrounded wf, hf), 0, 0 } -- image, bbox and area of a pseudo_bbox annotation.  Truncation toward zero.
+ *     pair_iou [row_cap] float64: with gt_xywh, the IoU (pycocotools bbIou, the operations of coco_ap.box_iou_xywh in float64) of the row's
+ *                      evaluation box with gt_xywh[b][r]; 0.0 without.
+ *     eval_boxes [eval_cap][4], eval_area, eval_score [eval_cap] float64: the first min(counts[b], max_det) rows of each image in row order
+ *                      (all scores tie and COCOeval's sort is stable): with cx, cy, w, h the wire integers, box = { cx - w / 2.0,
+ *                      cy - h / 2.0, w, h } (NOT truncated again), area = w * h, score = 1.0 -- cdetr_coco_match's dt_boxes / dt_area.
+ *   Every range is checked against row_cap / eval_cap (records) before anything is addressed: an image that does not fit writes NOTHING and
+ *   ORs a bit into *status (1: wire records, 2: evaluation records, 4: the offsets at `first` do not describe this store, 8: a count outside
+ *   0 .. R, taken as 0); offsets stop at the capacity.  counts[b] == 0 writes nothing and leaves the image's offsets equal.  The caller zeroes
+ *   *status once and raises when it reads the store back.  Limits: R <= 2^20, B <= 65535, CDETR_ERR_UNSUPPORTED beyond; first + B <= N;
+ *   capacities <= 2^30 records; wire 16-byte, points / pred_wh 8-byte aligned.                                                          */
+typedef struct {
+    int32_t B, R;               /* images in this batch, (padded) rows per image */
+    int32_t N, first;           /* images the store holds; store index of this batch's first image */
+    int32_t max_det;            /* cut of the evaluation records per image (COCOeval's maxDets[-1], 1100 in the reference) */
+    int32_t row_cap, eval_cap;  /* capacities in records */
+    int32_t pad_;
+    const float* points;        /* [B][R][2] normalised query points (x, y) */
+    const float* pred_wh;       /* [B][R][2] predicted normalised (w, h) */
+    const int32_t* counts;      /* [B] valid rows of each image; NULL = every row (a dense batch) */
+    const int32_t* orig_wh;     /* [B][2] original (width, height) in pixels */
+    const double* gt_xywh;      /* [B][R][4] ground-truth boxes in original pixels, same row padding; NULL = no pairing */
+    int32_t* img_counts;        /* [N] */
+    int32_t* row_off;           /* [N + 1] */
+    int32_t* eval_off;          /* [N + 1] */
+    int32_t* wire;              /* [row_cap][8] */
+    double* pair_iou;           /* [row_cap] */
+    double* eval_boxes;         /* [eval_cap][4] xywh */
+    double* eval_area;          /* [eval_cap] */
+    double* eval_score;         /* [eval_cap] */
+    int32_t* status;            /* [1] overflow bits, zeroed by the caller once */
+} cdetr_emit_pseudo_labels_desc;
+int cdetr_emit_pseudo_labels(const cdetr_emit_pseudo_labels_desc* d, void* stream);
+
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);
 /* Stream plumbing of the trainer (no reference counterpart: the reference runs one stream and drains it every step, A2/engine.py:33-57).

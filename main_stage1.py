@@ -7,6 +7,13 @@ and every 10 epochs), one JSON line per epoch in log.txt.
   --eval                   validation loss (A1/engine.py evaluate) of the model, then exit (A1's own --eval then unpacks a COCO evaluator
                            that evaluate never returns and crashes: not reproduced)
   --generate_pseudo_label  load --resume and write pseudo_bbox_{train,val,test}.json (the 2nd stage's training labels), then exit
+  --score_labels           with --generate_pseudo_label: box AP of the val / test files against instances_<split>.json (the offline
+                           evaluator's conventions, stage1.score_pseudo_labels) -> pseudo_scores_<split>.json
+  --test                   load --resume, forward val / test at the centres of their ground-truth boxes and score every predicted box against
+                           its own ground truth (stage1.score_boxes_at_gt) -> box_scores_<split>.json, then exit (A1's own --test reads
+                           outputs["pred_boxes"] through a PostProcess the 1st-stage model does not feed: not reproduced)
+  --device_labels          with either of the two: one cdetr_emit_pseudo_labels call per batch instead of the per-annotation host loop, one
+                           copy back per split, the scores straight from device memory; the same files byte for byte
   --auto_resume            continue from <output_dir>/checkpoint.pth: weights, AdamW moments, StepLR state and the next epoch
   --synthetic              seeded batches, no dataset
   --ragged_batches         batches may mix images with different numbers of points (padded to the batch maximum, per-image counts read by
@@ -57,14 +64,18 @@ def to_device(loader, device):
         yield {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in b.items()}
 
 
-def loader_for(args, split, points=False, shuffle=False, device=None):
+def loader_for(args, split, points=False, shuffle=False, device=None, boxes=False):
     """The split's DataLoader (host tensors).  --device_preprocess: its workers only decode and a data.Prefetcher on `device` yields device
-    batches whose image / mask come from one cdetr_image_prep launch -- the same tensors bit for bit."""
+    batches whose image / mask come from one cdetr_image_prep launch -- the same tensors bit for bit.  boxes=True (with points): the
+    points are the centres of the split's ground-truth boxes (data.FSC147BoxPointsDataset)."""
     from torch.utils.data import DataLoader
     from counting_detr_amd import data
     raw = bool(getattr(args, "device_preprocess", False))
     ragged = bool(getattr(args, "ragged_batches", False))
-    ds = data.build_points_dataset(args, split, raw=raw) if points else data.build_dataset_stage1(args, split, raw=raw)
+    if points and boxes:
+        ds = data.build_box_points_dataset(args, split, raw=raw)
+    else:
+        ds = data.build_points_dataset(args, split, raw=raw) if points else data.build_dataset_stage1(args, split, raw=raw)
     if ragged:
         collate_fn = data.collate_stage1_ragged_raw if raw else data.collate_stage1_ragged
     else:
@@ -100,6 +111,13 @@ def evaluate(model, criterion, loader, device):
     return {"loss": acc[0], "loss_wh": acc[1], "loss_giou": acc[2], "batches": n}
 
 
+def write_scores(path, scores):
+    """Print a score dict and write it as json (NaN for an undefined number, as json.dump spells it)."""
+    print(f"{path.name}:", json.dumps(scores))
+    with open(path, "w") as f:
+        json.dump(scores, f)
+
+
 def main(args):
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
@@ -114,7 +132,7 @@ def main(args):
         if not os.path.isfile(args.resume):
             args.resume = ""
 
-    if args.generate_pseudo_label:             # A1/main.py:247-272: the checkpoint as it is (strict=False), then the three splits
+    if args.generate_pseudo_label or args.test:  # A1/main.py:247-286: the checkpoint as it is (strict=False), then the splits
         ckpt = ckpt_io._read(args.resume)
         missing, unexpected = model.load_state_dict(ckpt["model"] if "model" in ckpt else ckpt, strict=False)
         ckpt_io.invalidate_caches(model)
@@ -122,9 +140,24 @@ def main(args):
             print("Missing Keys: {}".format(missing))
         if unexpected:
             print("Unexpected Keys: {}".format(unexpected))
+        if args.test:
+            for split in ("val", "test"):
+                scores = stage1.score_boxes_at_gt(model, loader_for(args, split, points=True, device=device, boxes=True), split,
+                                                  os.path.join(args.data_path, f"instances_{split}.json"), args.output_dir, device=device,
+                                                  device_labels=args.device_labels)
+                write_scores(output_dir / f"box_scores_{split}.json", scores)
+            return
         for split in ("train", "val", "test"):
-            ann = stage1.write_pseudo_labels(model, loader_for(args, split, points=True, device=device), split, args.output_dir, device=device)
+            ann, store = stage1.write_pseudo_labels(model, loader_for(args, split, points=True, device=device), split, args.output_dir,
+                                                    device=device, device_labels=args.device_labels, return_store=True)
             print(f"pseudo_bbox_{split}.json: {len(ann['images'])} images, {len(ann['annotations'])} boxes")
+            if not args.score_labels:
+                continue
+            gt_json = os.path.join(args.data_path, f"instances_{split}.json")
+            if split == "train" or not os.path.isfile(gt_json):
+                print(f"pseudo_bbox_{split}.json: not scored, the split has no box ground truth (instances_{split}.json)")
+                continue
+            write_scores(output_dir / f"pseudo_scores_{split}.json", stage1.score_pseudo_labels(ann, gt_json, store=store))
         return
 
     checkpoint = None
