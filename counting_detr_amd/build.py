@@ -24,7 +24,7 @@ def _hipcc():
 def _deps():
     inc = os.path.join(os.path.dirname(HERE), "include", "cdetr_hip.h")
     return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))] + \
-        [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rows.h"), os.path.join(CSRC, "dl_common.h"), inc]
+        [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rows.h"), os.path.join(CSRC, "dl_common.h"), os.path.join(CSRC, "records.h"), inc]
 
 
 def needs_build():

@@ -9,22 +9,13 @@
 // FMA (hipcc's default), so contraction is switched off for this translation unit.  No fast-math anywhere in the build.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "records.h"      // iou_xywh
 #include "../../include/cdetr_hip.h"
 
 namespace {
 
 constexpr int COCO_MAX_T = 16;        // IoU thresholds = waves of a workgroup
 constexpr int COCO_MAX_G = 4096;      // ground truths per image: 64 lanes x the 64 bits of a lane's taken-mask; 4 x 8 B x 4096 = 128 KiB of LDS
-
-// inter / union exactly as the host forms them (coco_ap.box_iou_xywh): da, ga = w * h; union = (da + ga) - inter
-__device__ __forceinline__ double iou_xywh(double dx, double dy, double dw, double dh, double da, double gx, double gy, double gw, double gh) {
-    const double w = fmin(dx + dw, gx + gw) - fmax(dx, gx);
-    const double h = fmin(dy + dh, gy + gh) - fmax(dy, gy);
-    const double inter = fmax(w, 0.0) * fmax(h, 0.0);
-    const double uni = (da + gw * gh) - inter;
-    return uni > 0.0 ? inter / uni : 0.0;
-}
 
 __global__ __launch_bounds__(256) void box_iou_kernel(const double* __restrict__ dt, int D, const double* __restrict__ gt, int G,
                                                       double* __restrict__ iou) {
@@ -34,7 +25,7 @@ __global__ __launch_bounds__(256) void box_iou_kernel(const double* __restrict__
     const double gx = gt[4 * (size_t)g], gy = gt[4 * (size_t)g + 1], gw = gt[4 * (size_t)g + 2], gh = gt[4 * (size_t)g + 3];
     for (int d = d0; d < min(d0 + 16, D); ++d) {
         const double dx = dt[4 * (size_t)d], dy = dt[4 * (size_t)d + 1], dw = dt[4 * (size_t)d + 2], dh = dt[4 * (size_t)d + 3];
-        iou[(size_t)d * G + g] = iou_xywh(dx, dy, dw, dh, dw * dh, gx, gy, gw, gh);
+        iou[(size_t)d * G + g] = iou_xywh(dx, dy, dw, dh, gx, gy, gw, gh);
     }
 }
 

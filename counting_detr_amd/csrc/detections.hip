@@ -10,36 +10,20 @@
 // off for this translation unit (as in coco_eval.hip).  No fast-math anywhere in the build.
 //
 // Placement is deterministic: a count kernel writes every image's number of kept queries, the emit kernel's workgroup b adds up the counts
-// of the images before it -- no atomic decides where a record lands (the only atomic is the OR into the status word).
+// of the images before it (records.h) -- no atomic decides where a record lands (the only atomic is the OR into the status word).
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "records.h"
 #include "../../include/cdetr_hip.h"
 
 namespace {
 
 constexpr int EMIT_MAX_Q = 4096;          // keys of one image in LDS: 4096 x 8 B = 32 KiB
-constexpr int EMIT_MAX_B = 65535;
-constexpr int EMIT_MAX_CAP = 1 << 30;     // records: running sums stay inside int32 (2^30 + 65535 x 4096 < 2^31)
 constexpr int EMIT_THREADS = 1024;
 constexpr int EMIT_WAVES = EMIT_THREADS / 64;
 
 // prob >= threshold, false for a NaN on either side (numpy's and torch's >=)
 __device__ __forceinline__ bool kept(float p, float thr) { return p >= thr; }
-
-// sum of `v` over the workgroup, the same value in every thread; `red` holds one int per wave.  Ends with a barrier-protected read: the
-// caller may reuse `red` after its next __syncthreads().
-__device__ __forceinline__ int block_sum(int v, int* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    int s = 0;
-    for (int w = 0; w < nw; ++w) s += red[w];
-    return s;
-}
 
 // counts[first + b] = number of kept queries of image b
 __global__ __launch_bounds__(256) void emit_count_kernel(cdetr_emit_detections_desc p) {
@@ -48,7 +32,7 @@ __global__ __launch_bounds__(256) void emit_count_kernel(cdetr_emit_detections_d
     const float* __restrict__ pr = p.prob + (size_t)b * p.Q;
     int n = 0;
     for (int q = threadIdx.x; q < p.Q; q += 256) n += kept(pr[q], p.threshold) ? 1 : 0;
-    n = block_sum(n, red);
+    n = block_sum<4>(n, red);
     if (threadIdx.x == 0) p.counts[p.first + b] = n;
 }
 
@@ -83,31 +67,20 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detection
     const int b = blockIdx.x, n = p.first + b;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
-    // where this image starts: the store's offsets at `first` (written by the previous call, in stream order) + the counts of the
-    // batch's images before this one
-    int sw = 0, se = 0;
-    for (int j = threadIdx.x; j < b; j += EMIT_THREADS) {
-        const int c = p.counts[p.first + j];
-        sw += c;
-        se += min(c, p.max_det);
-    }
-    sw = block_sum(sw, red);
-    se = block_sum(se, red);
-    const int start_w = p.wire_off[p.first], start_e = p.eval_off[p.first];
-    const int cnt = p.counts[n];
-    const int ecnt = min(cnt, p.max_det);
-    const bool start_ok = start_w >= 0 && start_w <= p.wire_cap && start_e >= 0 && start_e <= p.eval_cap;
-    const int w0 = start_w + sw, e0 = start_e + se;     // (start_ok: < 2^30 + B * Q, inside int32)
+    const auto at = place_records<EMIT_WAVES>([&](int j) { return p.counts[p.first + j]; }, b, p.Q, p.max_det, p.wire_off, p.eval_off, p.first,
+                                              p.wire_cap, p.eval_cap, red);
+    const int cnt = at.cnt, ecnt = at.ecnt;
     if (threadIdx.x == 0) {
-        p.wire_off[n + 1] = start_ok ? w0 + cnt : start_w;
-        p.eval_off[n + 1] = start_ok ? e0 + ecnt : start_e;
+        // the next offsets keep running past the capacities, UNclamped (cdetr_emit_pseudo_labels stops them at the capacity instead);
+        // with the start inside the store they are < 2^30 + B * Q, inside int32
+        p.wire_off[n + 1] = at.start_ok ? at.w0 + cnt : at.start_w;
+        p.eval_off[n + 1] = at.start_ok ? at.e0 + ecnt : at.start_e;
     }
-    const bool fits_w = start_ok && cnt >= 0 && cnt <= p.Q && w0 + cnt <= p.wire_cap;
-    const bool fits_e = start_ok && e0 + ecnt <= p.eval_cap;
-    if (!fits_w || !fits_e) {                           // uniform over the workgroup: nothing of this image is written
-        if (threadIdx.x == 0) atomicOr(p.status, !start_ok ? 4 : ((fits_w ? 0 : 1) | (fits_e ? 0 : 2)));
+    if (!at.fits()) {                                   // uniform over the workgroup: nothing of this image is written
+        if (threadIdx.x == 0) atomicOr(p.status, at.status_bits());
         return;
     }
+    const size_t w0 = (size_t)at.w0, e0 = (size_t)at.e0;
 
     const float* __restrict__ pr = p.prob + (size_t)b * p.Q;
     const float* __restrict__ bx = p.boxes + (size_t)b * p.Q * 4;
@@ -132,7 +105,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detection
         const int pos = done + before + __popcll(m & ((1ull << lane) - 1ull));
         if (k && pos < cnt) {
             const wire_fields f = wire_of(bx + 4 * (size_t)q, pt + 2 * (size_t)q, W, H);
-            int4* dst = reinterpret_cast<int4*>(p.wire + 8 * (size_t)(w0 + pos));
+            int4* dst = reinterpret_cast<int4*>(p.wire + 8 * (w0 + pos));
             dst[0] = make_int4(f.cx, f.cy, f.w, f.h);
             dst[1] = make_int4(f.area, f.px, f.py, __float_as_int(pq));
             key[pos] = sort_key(pq, q);
@@ -165,13 +138,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detection
         const int q = (int)(unsigned)(key[r] & 0xffffffffull);
         const wire_fields f = wire_of(bx + 4 * (size_t)q, pt + 2 * (size_t)q, W, H);
         const long long x2 = 2ll * f.cx - f.w, y2 = 2ll * f.cy - f.h;
-        double* bo = p.eval_boxes + 4 * (size_t)(e0 + r);
-        bo[0] = (double)(x2 / 2);
-        bo[1] = (double)(y2 / 2);
-        bo[2] = (double)f.w;
-        bo[3] = (double)f.h;
-        p.eval_area[e0 + r] = (double)((long long)f.w * (long long)f.h);
-        p.eval_score[e0 + r] = (double)pr[q];
+        write_eval_record(p.eval_boxes, p.eval_area, p.eval_score, e0 + r, (double)(x2 / 2), (double)(y2 / 2), f.w, f.h, (double)pr[q]);
     }
 }
 
@@ -179,23 +146,10 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detection
 
 extern "C" int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream) {
     CDETR_CHECK_ARG(d != nullptr, "cdetr_emit_detections: null descriptor");
-    CDETR_CHECK_ARG(d->B > 0 && d->Q > 0 && d->N > 0 && d->first >= 0 && d->max_det >= 0 && d->wire_cap >= 0 && d->eval_cap >= 0,
-                    "cdetr_emit_detections: bad sizes B = %d, Q = %d, N = %d, first = %d, max_det = %d, wire_cap = %d, eval_cap = %d", d->B, d->Q,
-                    d->N, d->first, d->max_det, d->wire_cap, d->eval_cap);
-    if (d->Q > EMIT_MAX_Q || d->B > EMIT_MAX_B) {
-        cdetr_set_error("cdetr_emit_detections: Q = %d queries (limit %d) or B = %d images per call (limit %d) not supported", d->Q, EMIT_MAX_Q, d->B,
-                        EMIT_MAX_B);
-        return CDETR_ERR_UNSUPPORTED;
-    }
-    CDETR_CHECK_ARG((int64_t)d->first + d->B <= d->N, "cdetr_emit_detections: images %d .. %d do not fit a store of N = %d", d->first,
-                    d->first + d->B - 1, d->N);
-    CDETR_CHECK_ARG(d->wire_cap <= EMIT_MAX_CAP && d->eval_cap <= EMIT_MAX_CAP, "cdetr_emit_detections: capacities %d / %d exceed %d records",
-                    d->wire_cap, d->eval_cap, EMIT_MAX_CAP);
-    CDETR_CHECK_ARG(d->prob && d->boxes && d->points && d->orig_hw, "cdetr_emit_detections: null input pointer");
-    CDETR_CHECK_ARG(d->counts && d->wire_off && d->eval_off && d->status, "cdetr_emit_detections: null counts / offset table / status pointer");
-    CDETR_CHECK_ARG(d->wire_cap == 0 || d->wire, "cdetr_emit_detections: null wire-record pointer");
-    CDETR_CHECK_ARG(d->eval_cap == 0 || (d->eval_boxes && d->eval_area && d->eval_score), "cdetr_emit_detections: null evaluation-record pointer");
-    CDETR_CHECK_ARG((reinterpret_cast<uintptr_t>(d->wire) & 15) == 0, "cdetr_emit_detections: wire records must be 16-byte aligned");
+    if (const int rc = check_record_store("cdetr_emit_detections", "Q", "queries", "wire_cap", "wire-record", d->B, d->Q, EMIT_MAX_Q, d->N, d->first,
+                                          d->max_det, d->wire_cap, d->eval_cap, d->prob && d->boxes && d->points && d->orig_hw, d->counts, d->wire_off,
+                                          d->eval_off, d->status, d->wire, d->wire != nullptr, d->eval_boxes, d->eval_area, d->eval_score))
+        return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(emit_count_kernel, dim3(d->B), dim3(256), 0, s, *d);
     hipLaunchKernelGGL(emit_kernel, dim3(d->B), dim3(EMIT_THREADS), 0, s, *d);

@@ -1985,6 +1985,29 @@ def lsap(cost, plan):
     return idx_i, idx_j, status
 
 
+def _expect(fn, dtype, **tensors):
+    """The evaluation-side wrappers' argument check: every named tensor is contiguous and of `dtype` (None: an optional one left out)."""
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"{fn}: expected a contiguous {dtype} tensor for `{name}`, got {t.dtype}")
+
+
+class _between:
+    """`with _between(events):` around ONE library call: the optional pair of torch.cuda.Event is recorded right before / after it."""
+
+    def __init__(self, events):
+        self.events = events
+
+    def __enter__(self):
+        if self.events is not None:
+            self.events[0].record()
+
+    def __exit__(self, exc_type, *exc):
+        if self.events is not None and exc_type is None:
+            self.events[1].record()
+        return False
+
+
 def box_iou_xywh(dt, gt):
     """cdetr_box_iou_xywh: float64 IoU matrix [D, G] of xywh boxes dt [D, 4], gt [G, 4] (device tensors), equal to
     coco_ap.box_iou_xywh's numpy result bit for bit."""
@@ -2007,10 +2030,9 @@ def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, 
     dev = gt_off.device
     B, T, A = gt_off.numel() - 1, iou_thrs.numel(), area_rng.numel() // 2
     G, D = gt_area.numel(), dt_area.numel()
-    for t, dt_ in ((gt_boxes, torch.float64), (gt_area, torch.float64), (dt_boxes, torch.float64), (dt_area, torch.float64), (iou_thrs, torch.float64),
-                   (area_rng, torch.float64), (gt_ignore, torch.uint8), (gt_off, torch.int32), (dt_off, torch.int32)):
-        if t.dtype != dt_ or not t.is_contiguous():
-            raise RuntimeError(f"coco_match: expected a contiguous {dt_} tensor, got {t.dtype}")
+    _expect("coco_match", torch.float64, gt_boxes=gt_boxes, gt_area=gt_area, dt_boxes=dt_boxes, dt_area=dt_area, iou_thrs=iou_thrs, area_rng=area_rng)
+    _expect("coco_match", torch.uint8, gt_ignore=gt_ignore)
+    _expect("coco_match", torch.int32, gt_off=gt_off, dt_off=dt_off)
     if gt_boxes.numel() != 4 * G or gt_ignore.numel() != G or dt_boxes.numel() != 4 * D or dt_off.numel() != B + 1:
         raise RuntimeError("coco_match: packed arrays of inconsistent sizes")
     n_flag = A * T * D
@@ -2022,11 +2044,8 @@ def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, 
     d.dt_boxes, d.dt_area, d.dt_off = ptr(dt_boxes), ptr(dt_area), ptr(dt_off)
     d.iou_thrs, d.area_rng = ptr(iou_thrs), ptr(area_rng)
     d.matched, d.det_ignored, d.npig = buf.data_ptr(), buf.data_ptr() + n_flag, buf.data_ptr() + n_pad
-    if events is not None:
-        events[0].record()
-    check(lib().cdetr_coco_match(C.byref(d), stream_ptr()), "cdetr_coco_match")
-    if events is not None:
-        events[1].record()
+    with _between(events):
+        check(lib().cdetr_coco_match(C.byref(d), stream_ptr()), "cdetr_coco_match")
     if host:
         h = buf.cpu().numpy()
         return (h[:n_flag].reshape(A, T, D).astype(bool), h[n_flag:2 * n_flag].reshape(A, T, D).astype(bool),
@@ -2041,9 +2060,9 @@ def image_prep(raw, events=None):
     both outputs.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/image_prep_time.py)."""
     from ._ffi import ImagePrepDesc
     pixels, images, tables, lut = raw["pixels"], raw["images"], raw["tables"], raw["lut"]
-    for name, t, dt_ in (("pixels", pixels, torch.uint8), ("images", images, torch.int32), ("tables", tables, torch.int32), ("lut", lut, torch.float32)):
-        if t.dtype != dt_ or not t.is_contiguous():
-            raise RuntimeError(f"image_prep: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    _expect("image_prep", torch.uint8, pixels=pixels)
+    _expect("image_prep", torch.int32, images=images, tables=tables)
+    _expect("image_prep", torch.float32, lut=lut)
     if images.dim() != 2 or images.shape[1] != 12 or lut.numel() != 768:
         raise RuntimeError(f"image_prep: `images` must be [B, 12] and `lut` [3, 256], got {tuple(images.shape)} and {tuple(lut.shape)}")
     B, Hm, Wm = images.shape[0], int(raw["Hm"]), int(raw["Wm"])
@@ -2053,11 +2072,8 @@ def image_prep(raw, events=None):
     d.B, d.Hm, d.Wm, d.max_taps, d.max_rows = B, Hm, Wm, int(raw["max_taps"]), int(raw["max_rows"])
     d.pixels, d.pixel_bytes, d.images, d.tables, d.table_ints = ptr(pixels), pixels.numel(), ptr(images), ptr(tables), tables.numel()
     d.lut, d.image, d.mask = ptr(lut), ptr(image), ptr(mask)
-    if events is not None:
-        events[0].record()
-    check(lib().cdetr_image_prep(C.byref(d), stream_ptr()), "cdetr_image_prep")
-    if events is not None:
-        events[1].record()
+    with _between(events):
+        check(lib().cdetr_image_prep(C.byref(d), stream_ptr()), "cdetr_image_prep")
     return image, mask
 
 
@@ -2067,9 +2083,8 @@ def emit_detections(prob, boxes, points, orig_hw, store, first, events=None):
     int32 [B, 2] = (height, width).  One call on the current stream, nothing comes back to the host; a record range that does not fit the
     store sets its status word (DetectionStore.finish raises).  events: a pair of torch.cuda.Event recorded right before / after the call."""
     from ._ffi import EmitDetectionsDesc
-    for name, t, dt_ in (("prob", prob, torch.float32), ("boxes", boxes, torch.float32), ("points", points, torch.float32), ("orig_hw", orig_hw, torch.int32)):
-        if t.dtype != dt_ or not t.is_contiguous():
-            raise RuntimeError(f"emit_detections: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    _expect("emit_detections", torch.float32, prob=prob, boxes=boxes, points=points)
+    _expect("emit_detections", torch.int32, orig_hw=orig_hw)
     if prob.dim() != 2 or tuple(boxes.shape) != tuple(prob.shape) + (4,) or tuple(points.shape) != tuple(prob.shape) + (2,) \
             or tuple(orig_hw.shape) != (prob.shape[0], 2):
         raise RuntimeError(f"emit_detections: prob [B, Q], boxes [B, Q, 4], points [B, Q, 2], orig_hw [B, 2] expected, got {tuple(prob.shape)}, "
@@ -2083,18 +2098,70 @@ def emit_detections(prob, boxes, points, orig_hw, store, first, events=None):
     d.prob, d.boxes, d.points, d.orig_hw = ptr(prob), ptr(boxes), ptr(points), ptr(orig_hw)
     d.counts, d.wire_off, d.eval_off, d.status = ptr(store.counts), ptr(store.wire_off), ptr(store.eval_off), ptr(store.status)
     d.wire, d.eval_boxes, d.eval_area, d.eval_score = ptr(store.wire), ptr(store.eval_boxes), ptr(store.eval_area), ptr(store.eval_score)
-    if events is not None:
-        events[0].record()
-    check(lib().cdetr_emit_detections(C.byref(d), stream_ptr()), "cdetr_emit_detections")
-    if events is not None:
-        events[1].record()
+    with _between(events):
+        check(lib().cdetr_emit_detections(C.byref(d), stream_ptr()), "cdetr_emit_detections")
 
 
-class DetectionStore:
-    """The detections of a whole split on the device, filled batch by batch by cdetr_emit_detections (`emit`) and read back ONCE (`finish`).
-    One byte buffer: [status | counts [N] | wire_off [N + 1] | eval_off [N + 1] | eval_score f64 [eval_cap] | wire int32 [wire_cap, 8]] is what
-    `finish` copies; [eval_boxes f64 [eval_cap, 4] | eval_area f64 [eval_cap]] behind it never leaves the device (coco_ap.summarize_store hands
-    them to cdetr_coco_match).  Capacities default to the worst case, N * Q wire and N * min(Q, max_det) evaluation records."""
+class _RecordStore:
+    """The records of a whole split on the device, filled batch by batch by an emit entry (`emit`) and read back ONCE (`finish`).  One byte
+    buffer in 16-byte aligned sections: [status | counts [N] | wire offsets [N + 1] | eval_off [N + 1] | eval_score f64 [eval_cap] | wire
+    int32 [wire records, 8] | `_extra`: a subclass's sections per wire record] is what `finish` copies; [eval_boxes f64 [eval_cap, 4] |
+    eval_area f64 [eval_cap]] behind it never leaves the device (coco_ap.summarize_store hands them to cdetr_coco_match)."""
+    _extra = ()
+
+    def _cut(self, device):
+        N, E, W, i32, f64 = self.N, self.eval_cap, getattr(self, self._cap), torch.int32, torch.float64
+        sections = [("status", i32, 1), ("counts", i32, N), (self._off, i32, N + 1), ("eval_off", i32, N + 1), ("eval_score", f64, E),
+                    ("wire", i32, 8 * W), *((name, dt_, W) for name, dt_ in self._extra), ("eval_boxes", f64, 4 * E), ("eval_area", f64, E)]
+        cuts = [0]
+        for _, dt_, n in sections:
+            cuts.append(cuts[-1] + (n * dt_.itemsize + 15) // 16 * 16)
+        self.buf = torch.empty(cuts[-1], dtype=torch.uint8, device=device)
+        self.buf[:cuts[4]].zero_()                                                                             # status, counts, both offsets' [0]
+        for lo, (name, dt_, n) in zip(cuts, sections):
+            setattr(self, name, self.buf[lo:lo + n * dt_.itemsize].view(dt_))
+        self.wire, self.eval_boxes = self.wire.view(-1, 8), self.eval_boxes.view(-1, 4)
+        self._cuts, self.first, self._host = cuts, 0, None
+
+    def emit(self, *batch, **kw):
+        """Append one forwarded batch: the tensors and keywords of the store's emit function (emit_detections / emit_pseudo_labels) without
+        `store` and `first`; returns the store index of the batch's first image."""
+        first, B = self.first, batch[0].shape[0]
+        if first + B > self.N:
+            raise RuntimeError(f"{type(self).__name__}: image {first + B} into a store of {self.N}")
+        globals()[self._emit](*batch[:4], self, first, *batch[4:], **kw)
+        self.first, self._host = first + B, None
+        return first
+
+    def finish(self):
+        """ONE device -> host copy (it waits for the emits): dict of numpy arrays for the n images emitted so far -- counts [n], the wire
+        offsets / eval_off [n + 1], the W wire records as the subclass names them, its sections per wire record, eval_score f64 [E].
+        Raises if a record range did not fit the store."""
+        if self._host is None:
+            c, n = self._cuts, self.first
+            h = self.buf[:c[-3]].cpu().numpy()                                                                 # up to eval_boxes
+            status = int(h[:4].view("int32")[0])
+            if status:
+                raise RuntimeError(self._status.format(status=status, wire_cap=getattr(self, self._cap), eval_cap=self.eval_cap))
+            i32 = lambda k, m: h[c[k]:c[k] + 4 * m].view("int32")                                              # noqa: E731
+            wire_off, eval_off = i32(2, n + 1), i32(3, n + 1)
+            W, E = int(wire_off[n]), int(eval_off[n])
+            host = {"counts": i32(1, n), self._off: wire_off, "eval_off": eval_off}
+            host.update(self._wire_view(h[c[5]:c[5] + 32 * W].view("int32").reshape(W, 8)))
+            for k, (name, dt_) in enumerate(self._extra, 6):
+                host[name] = torch.from_numpy(h[c[k]:c[k] + dt_.itemsize * W]).view(dt_).numpy()
+            host["eval_score"] = h[c[4]:c[4] + 8 * E].view("float64")
+            self._host = host
+        return self._host
+
+
+class DetectionStore(_RecordStore):
+    """The detections of a whole split, filled by cdetr_emit_detections.  `finish` gives wire int32 [W, 7] (cx, cy, w, h, area, px, py) and
+    score fp32 [W].  Capacities default to the worst case, N * Q wire and N * min(Q, max_det) evaluation records."""
+    _off, _cap, _emit = "wire_off", "wire_cap", "emit_detections"
+    _wire_view = staticmethod(lambda rec: {"wire": rec[:, :7], "score": rec[:, 7].view("float32")})
+    _status = ("DetectionStore: cdetr_emit_detections reported status {status} (1: more than {wire_cap} wire records, "
+               "2: more than {eval_cap} evaluation records, 4: inconsistent offsets); the images concerned were not written")
 
     def __init__(self, n_images, n_queries, device, threshold=0.5, max_det=1100, wire_cap=None, eval_cap=None):
         self.N, self.Q, self.threshold, self.max_det = int(n_images), int(n_queries), float(threshold), int(max_det)
@@ -2104,46 +2171,7 @@ class DetectionStore:
         self.eval_cap = self.N * min(self.Q, self.max_det) if eval_cap is None else int(eval_cap)
         if max(self.wire_cap, self.eval_cap) > 1 << 30:
             raise RuntimeError(f"DetectionStore: {self.wire_cap} / {self.eval_cap} records exceed the 2^30 of cdetr_emit_detections")
-        al = lambda n: (n + 15) // 16 * 16                                                                     # noqa: E731
-        N, cuts = self.N, [0]
-        for nbytes in (16, 4 * N, 4 * (N + 1), 4 * (N + 1), 8 * self.eval_cap, 32 * self.wire_cap, 32 * self.eval_cap, 8 * self.eval_cap):
-            cuts.append(cuts[-1] + al(nbytes))
-        self.buf = torch.empty(cuts[-1], dtype=torch.uint8, device=device)
-        self.buf[:cuts[4]].zero_()                                                                             # status, counts, wire_off[0], eval_off[0]
-        part = lambda k, dt_, n: self.buf[cuts[k]:cuts[k + 1]].view(dt_)[:n]                                   # noqa: E731
-        self.status, self.counts = part(0, torch.int32, 1), part(1, torch.int32, N)
-        self.wire_off, self.eval_off = part(2, torch.int32, N + 1), part(3, torch.int32, N + 1)
-        self.eval_score, self.wire = part(4, torch.float64, self.eval_cap), part(5, torch.int32, 8 * self.wire_cap).view(-1, 8)
-        self.eval_boxes, self.eval_area = part(6, torch.float64, 4 * self.eval_cap).view(-1, 4), part(7, torch.float64, self.eval_cap)
-        self._cuts, self.first, self._host = cuts, 0, None
-
-    def emit(self, prob, boxes, points, orig_hw, events=None):
-        """Append one forwarded batch (see emit_detections); returns the store index of its first image."""
-        first, B = self.first, prob.shape[0]
-        if first + B > self.N:
-            raise RuntimeError(f"DetectionStore: image {first + B} into a store of {self.N}")
-        emit_detections(prob, boxes, points, orig_hw, self, first, events=events)
-        self.first, self._host = first + B, None
-        return first
-
-    def finish(self):
-        """ONE device -> host copy (it waits for the emits): dict of numpy arrays for the n images emitted so far -- counts [n], wire_off /
-        eval_off [n + 1], wire int32 [W, 7] (cx, cy, w, h, area, px, py), score fp32 [W], eval_score f64 [E].  Raises if a record range did
-        not fit the store."""
-        if self._host is None:
-            c, n = self._cuts, self.first
-            h = self.buf[:c[6]].cpu().numpy()
-            status = int(h[:4].view("int32")[0])
-            if status:
-                raise RuntimeError(f"DetectionStore: cdetr_emit_detections reported status {status} (1: more than {self.wire_cap} wire records, "
-                                   f"2: more than {self.eval_cap} evaluation records, 4: inconsistent offsets); the images concerned were not written")
-            i32 = lambda k, m: h[c[k]:c[k] + 4 * m].view("int32")                                              # noqa: E731
-            wire_off, eval_off = i32(2, n + 1), i32(3, n + 1)
-            W, E = int(wire_off[n]), int(eval_off[n])
-            rec = h[c[5]:c[5] + 32 * W].view("int32").reshape(W, 8)
-            self._host = {"counts": i32(1, n), "wire_off": wire_off, "eval_off": eval_off, "wire": rec[:, :7], "score": rec[:, 7].view("float32"),
-                          "eval_score": h[c[4]:c[4] + 8 * E].view("float64")}
-        return self._host
+        self._cut(device)
 
 
 def emit_pseudo_labels(points, pred_wh, counts, orig_wh, store, first, gt_xywh=None, events=None):
@@ -2153,10 +2181,9 @@ def emit_pseudo_labels(points, pred_wh, counts, orig_wh, store, first, gt_xywh=N
     stream, nothing comes back to the host; a record range that does not fit the store sets its status word (PseudoLabelStore.finish
     raises).  events: a pair of torch.cuda.Event recorded right before / after the call."""
     from ._ffi import EmitPseudoLabelsDesc
-    for name, t, dt_ in (("points", points, torch.float32), ("pred_wh", pred_wh, torch.float32), ("counts", counts, torch.int32),
-                         ("orig_wh", orig_wh, torch.int32), ("gt_xywh", gt_xywh, torch.float64)):
-        if t is not None and (t.dtype != dt_ or not t.is_contiguous()):
-            raise RuntimeError(f"emit_pseudo_labels: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    _expect("emit_pseudo_labels", torch.float32, points=points, pred_wh=pred_wh)
+    _expect("emit_pseudo_labels", torch.int32, counts=counts, orig_wh=orig_wh)
+    _expect("emit_pseudo_labels", torch.float64, gt_xywh=gt_xywh)
     if points.dim() != 3 or points.shape[2] != 2 or tuple(pred_wh.shape) != tuple(points.shape) or tuple(orig_wh.shape) != (points.shape[0], 2) \
             or (counts is not None and tuple(counts.shape) != (points.shape[0],)) \
             or (gt_xywh is not None and tuple(gt_xywh.shape) != tuple(points.shape[:2]) + (4,)):
@@ -2175,19 +2202,19 @@ def emit_pseudo_labels(points, pred_wh, counts, orig_wh, store, first, gt_xywh=N
     d.img_counts, d.row_off, d.eval_off, d.status = ptr(store.counts), ptr(store.row_off), ptr(store.eval_off), ptr(store.status)
     d.wire, d.pair_iou = ptr(store.wire), ptr(store.pair_iou)
     d.eval_boxes, d.eval_area, d.eval_score = ptr(store.eval_boxes), ptr(store.eval_area), ptr(store.eval_score)
-    if events is not None:
-        events[0].record()
-    check(lib().cdetr_emit_pseudo_labels(C.byref(d), stream_ptr()), "cdetr_emit_pseudo_labels")
-    if events is not None:
-        events[1].record()
+    with _between(events):
+        check(lib().cdetr_emit_pseudo_labels(C.byref(d), stream_ptr()), "cdetr_emit_pseudo_labels")
 
 
-class PseudoLabelStore:
-    """The stage-1 pseudo labels of a whole split on the device, filled batch by batch by cdetr_emit_pseudo_labels (`emit`) and read back ONCE
-    (`finish`).  One byte buffer: [status | counts [N] | row_off [N + 1] | eval_off [N + 1] | eval_score f64 [eval_cap] | wire int32 [row_cap, 8]
-    | pair_iou f64 [row_cap]] is what `finish` copies; [eval_boxes f64 [eval_cap, 4] | eval_area f64 [eval_cap]] behind it never leaves the
-    device (coco_ap.summarize_store hands them to cdetr_coco_match: the store carries the members coco_ap.pack_store reads of a
-    DetectionStore).  row_cap = the rows (annotated dots) of the split; at most min(row_cap, N * max_det) of them become evaluation records."""
+class PseudoLabelStore(_RecordStore):
+    """The stage-1 pseudo labels of a whole split, filled by cdetr_emit_pseudo_labels, with pair_iou f64 [row_cap] behind the wire records.
+    `finish` gives wire int32 [W, 6] (store image index, cx, cy, w, h, area) and pair_iou f64 [W].  row_cap = the rows (annotated dots) of
+    the split; at most min(row_cap, N * max_det) of them become evaluation records."""
+    _off, _cap, _emit, _extra = "row_off", "row_cap", "emit_pseudo_labels", (("pair_iou", torch.float64),)
+    _wire_view = staticmethod(lambda rec: {"wire": rec[:, :6]})
+    _status = ("PseudoLabelStore: cdetr_emit_pseudo_labels reported status {status} (1: more than {wire_cap} wire records, "
+               "2: more than {eval_cap} evaluation records, 4: inconsistent offsets, 8: a count outside the batch's rows); "
+               "the images concerned were not written")
 
     def __init__(self, n_images, row_cap, device, max_det=1100):
         self.N, self.row_cap, self.max_det = int(n_images), int(row_cap), int(max_det)
@@ -2196,49 +2223,7 @@ class PseudoLabelStore:
         self.eval_cap = min(self.row_cap, self.N * self.max_det)
         if self.row_cap > 1 << 30:
             raise RuntimeError(f"PseudoLabelStore: {self.row_cap} records exceed the 2^30 of cdetr_emit_pseudo_labels")
-        al = lambda n: (n + 15) // 16 * 16                                                                     # noqa: E731
-        N, cuts = self.N, [0]
-        for nbytes in (16, 4 * N, 4 * (N + 1), 4 * (N + 1), 8 * self.eval_cap, 32 * self.row_cap, 8 * self.row_cap, 32 * self.eval_cap,
-                       8 * self.eval_cap):
-            cuts.append(cuts[-1] + al(nbytes))
-        self.buf = torch.empty(cuts[-1], dtype=torch.uint8, device=device)
-        self.buf[:cuts[4]].zero_()                                                                             # status, counts, row_off[0], eval_off[0]
-        part = lambda k, dt_, n: self.buf[cuts[k]:cuts[k + 1]].view(dt_)[:n]                                   # noqa: E731
-        self.status, self.counts = part(0, torch.int32, 1), part(1, torch.int32, N)
-        self.row_off, self.eval_off = part(2, torch.int32, N + 1), part(3, torch.int32, N + 1)
-        self.eval_score, self.wire = part(4, torch.float64, self.eval_cap), part(5, torch.int32, 8 * self.row_cap).view(-1, 8)
-        self.pair_iou = part(6, torch.float64, self.row_cap)
-        self.eval_boxes, self.eval_area = part(7, torch.float64, 4 * self.eval_cap).view(-1, 4), part(8, torch.float64, self.eval_cap)
-        self._cuts, self.first, self._host = cuts, 0, None
-
-    def emit(self, points, pred_wh, counts, orig_wh, gt_xywh=None, events=None):
-        """Append one forwarded batch (see emit_pseudo_labels); returns the store index of its first image."""
-        first, B = self.first, points.shape[0]
-        if first + B > self.N:
-            raise RuntimeError(f"PseudoLabelStore: image {first + B} into a store of {self.N}")
-        emit_pseudo_labels(points, pred_wh, counts, orig_wh, self, first, gt_xywh=gt_xywh, events=events)
-        self.first, self._host = first + B, None
-        return first
-
-    def finish(self):
-        """ONE device -> host copy (it waits for the emits): dict of numpy arrays for the n images emitted so far -- counts [n], row_off /
-        eval_off [n + 1], wire int32 [W, 6] (store image index, cx, cy, w, h, area), pair_iou f64 [W], eval_score f64 [E].  Raises if a
-        record range did not fit the store."""
-        if self._host is None:
-            c, n = self._cuts, self.first
-            h = self.buf[:c[7]].cpu().numpy()
-            status = int(h[:4].view("int32")[0])
-            if status:
-                raise RuntimeError(f"PseudoLabelStore: cdetr_emit_pseudo_labels reported status {status} (1: more than {self.row_cap} wire records, "
-                                   f"2: more than {self.eval_cap} evaluation records, 4: inconsistent offsets, 8: a count outside the batch's rows); "
-                                   "the images concerned were not written")
-            i32 = lambda k, m: h[c[k]:c[k] + 4 * m].view("int32")                                              # noqa: E731
-            row_off, eval_off = i32(2, n + 1), i32(3, n + 1)
-            W, E = int(row_off[n]), int(eval_off[n])
-            self._host = {"counts": i32(1, n), "row_off": row_off, "eval_off": eval_off,
-                          "wire": h[c[5]:c[5] + 32 * W].view("int32").reshape(W, 8)[:, :6], "pair_iou": h[c[6]:c[6] + 8 * W].view("float64"),
-                          "eval_score": h[c[4]:c[4] + 8 * E].view("float64")}
-        return self._host
+        self._cut(device)
 
 
 class CriterionFn(torch.autograd.Function):
@@ -2303,11 +2288,8 @@ def criterion_eval(logits, boxes, pvars, tgt_boxes, tgt_labels, plan, idx_i, idx
         raise RuntimeError(f"criterion_eval: logits [{B}, {Q}, {Cc}] with a plan of B = {plan.B}, Q = {plan.Q}, Mmax = {plan.Mmax} and indices "
                            f"{tuple(idx_i.shape)}, {tuple(idx_j.shape)}")
     logits, boxes, pvars = logits.detach().contiguous(), boxes.detach().contiguous(), pvars.detach().contiguous()
-    for name, t, dt_ in (("logits", logits, torch.float32), ("boxes", boxes, torch.float32), ("vars", pvars, torch.float32),
-                         ("tgt_boxes", tgt_boxes, torch.float32), ("tgt_labels", tgt_labels, torch.int64), ("idx_i", idx_i, torch.int64),
-                         ("idx_j", idx_j, torch.int64)):
-        if t.dtype != dt_ or not t.is_contiguous():
-            raise RuntimeError(f"criterion_eval: expected a contiguous {dt_} tensor for `{name}`, got {t.dtype}")
+    _expect("criterion_eval", torch.float32, logits=logits, boxes=boxes, vars=pvars, tgt_boxes=tgt_boxes)
+    _expect("criterion_eval", torch.int64, tgt_labels=tgt_labels, idx_i=idx_i, idx_j=idx_j)
     if tuple(boxes.shape) != (B, Q, 4) or tuple(pvars.shape) != (B, Q, 2):
         raise RuntimeError(f"criterion_eval: boxes [B, Q, 4] and vars [B, Q, 2] expected, got {tuple(boxes.shape)}, {tuple(pvars.shape)}")
     if out is None:
@@ -2320,11 +2302,8 @@ def criterion_eval(logits, boxes, pvars, tgt_boxes, tgt_labels, plan, idx_i, idx
     d.tgt_boxes = ptr(tgt_boxes) if tgt_boxes.numel() else ptr(out)             # never read without targets
     d.tgt_labels = ptr(tgt_labels) if tgt_labels.numel() else ptr(out)
     d.tgt_off, d.idx_i, d.idx_j, d.losses, d.loss_weights = ptr(plan.tgt_off), ptr(idx_i), ptr(idx_j), ptr(out), ptr(w6)
-    if events is not None:
-        events[0].record()
-    check(lib().cdetr_criterion_eval(C.byref(d), stream_ptr()), "cdetr_criterion_eval")
-    if events is not None:
-        events[1].record()
+    with _between(events):
+        check(lib().cdetr_criterion_eval(C.byref(d), stream_ptr()), "cdetr_criterion_eval")
     return out
 
 

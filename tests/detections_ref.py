@@ -33,21 +33,38 @@ def emit_image(prob, boxes, points, ori_h, ori_w, threshold, max_det):
             "eval_area": (w * h).astype(np.float64), "eval_score": score[order].astype(np.float64)}
 
 
-def emit_store(batches, threshold, max_det):
+def emit_store(batches, threshold, max_det, wire_cap=None, eval_cap=None):
     """A sequence of launches, each (prob [B, Q], boxes [B, Q, 4], points [B, Q, 2], orig_hw [B, 2] = (height, width)) -> what
-    ops.DetectionStore.finish returns after them, plus eval_boxes / eval_area (device-resident there) and the per-image dicts."""
-    imgs = []
+    ops.DetectionStore.finish returns after them, plus eval_boxes / eval_area (device-resident there) and the per-image dicts.
+
+    wire_cap / eval_cap (records; None: room for everything): the kernel's rule for a store that may overflow.  A launch starts at the
+    offsets the launch before it left; inside a launch an image lands behind the launch's earlier images, whether those fitted or not, and
+    its next offsets are start + those counts + its own: they run on past a capacity, UNclamped.  An image that does not fit both sections
+    writes nothing and ORs 1 (wire records) | 2 (evaluation records) into `status`; a launch whose start lies beyond a capacity writes
+    nothing, repeats its start as every next offset and ORs 4.  `placed`: per image (first wire record, first evaluation record) or None;
+    the concatenated record arrays hold the placed images only; `counts` are the images' own either way."""
+    imgs, placed, status, wire_off, eval_off = [], [], 0, [0], [0]
     for prob, boxes, points, orig_hw in batches:
+        sw, se = wire_off[-1], eval_off[-1]
+        start_ok = (wire_cap is None or sw <= wire_cap) and (eval_cap is None or se <= eval_cap)
+        w0, e0 = sw, se
         for b in range(len(prob)):
-            imgs.append(emit_image(prob[b], boxes[b], points[b], orig_hw[b][0], orig_hw[b][1], threshold, max_det))
-    cat = lambda k, shape, dt: (np.concatenate([i[k] for i in imgs]) if imgs else np.zeros(0)).reshape(shape).astype(dt)      # noqa: E731
-    counts = np.array([len(i["q"]) for i in imgs], dtype=np.int32)
-    return {"counts": counts,
-            "wire_off": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
-            "eval_off": np.concatenate([[0], np.cumsum([len(i["eval_q"]) for i in imgs])]).astype(np.int32),
+            im = emit_image(prob[b], boxes[b], points[b], orig_hw[b][0], orig_hw[b][1], threshold, max_det)
+            imgs.append(im)
+            w1, e1 = w0 + len(im["q"]), e0 + len(im["eval_q"])
+            fits_w, fits_e = start_ok and (wire_cap is None or w1 <= wire_cap), start_ok and (eval_cap is None or e1 <= eval_cap)
+            placed.append((w0, e0) if fits_w and fits_e else None)
+            status |= 4 if not start_ok else (0 if fits_w else 1) | (0 if fits_e else 2)
+            wire_off.append(w1 if start_ok else sw)
+            eval_off.append(e1 if start_ok else se)
+            w0, e0 = w1, e1
+    put = [i for i, at in zip(imgs, placed) if at]
+    cat = lambda k, shape, dt: (np.concatenate([i[k] for i in put]) if put else np.zeros(0)).reshape(shape).astype(dt)      # noqa: E731
+    return {"counts": np.array([len(i["q"]) for i in imgs], dtype=np.int32),
+            "wire_off": np.array(wire_off, dtype=np.int32), "eval_off": np.array(eval_off, dtype=np.int32),
             "wire": cat("wire", (-1, 7), np.int32), "score": cat("score", (-1,), F32),
             "eval_boxes": cat("eval_boxes", (-1, 4), np.float64), "eval_area": cat("eval_area", (-1,), np.float64),
-            "eval_score": cat("eval_score", (-1,), np.float64), "images": imgs}
+            "eval_score": cat("eval_score", (-1,), np.float64), "images": imgs, "placed": placed, "status": status}
 
 
 def make_case(rng, Q, hw, kept="some", ties=0, at_threshold=False, nan=False, negative_corner=True, threshold=0.5):

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -38,24 +40,13 @@ def test_ffi_export_list_matches_header(libpath):
 
 
 def test_struct_fields_match_header():
+    """Every ctypes.Structure of _ffi names the fields of its header struct, in the header's order."""
     from counting_detr_amd import _ffi
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
-
-    def fields(struct_name):
-        body = re.search(r"typedef struct \{([^}]*)\}\s*" + struct_name + r"\s*;", src, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        out = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for nm in decl.split(","):
-                out.append(re.findall(r"(\w+)\s*$", nm.strip())[0])
-        return out
-    for cname, cls in (("cdetr_conv_geom", _ffi.ConvGeom), ("cdetr_gemm_desc", _ffi.GemmDesc),
-                       ("cdetr_wgrad_desc", _ffi.WgradDesc), ("cdetr_rcda_fwd_desc", _ffi.RcdaFwdDesc),
-                       ("cdetr_rcda_bwd_desc", _ffi.RcdaBwdDesc), ("cdetr_mirror_item", _ffi.MirrorItem), ("cdetr_criterion_desc", _ffi.CriterionDesc)):
-        assert fields(cname) == [f[0] for f in cls._fields_], cname
+    twins = [c for c in vars(_ffi).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure]
+    assert len(twins) == 13 and _ffi.ConvGeom in twins and _ffi.EmitPseudoLabelsDesc in twins
+    assert abi_header.header_name(_ffi.RcdaFwdDesc) == "cdetr_rcda_fwd_desc" and abi_header.header_name(_ffi.MirrorItem) == "cdetr_mirror_item"
+    for cls in twins:
+        assert abi_header.field_names(abi_header.header_name(cls)) == [f[0] for f in cls._fields_], cls.__name__
 
 
 def test_error_reporting_without_gpu(libpath):

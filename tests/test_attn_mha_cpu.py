@@ -1,12 +1,9 @@
 """attention_type "nn.MultiheadAttention" without a GPU: the model builds with exactly the reference variant's state dict
 (tests/golden/g13_attn_mha.npz), loads it strictly, stage 1 refuses the variant, and the C ABI of cdetr_attn_* matches its ctypes twin."""
-import os
-import re
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
 
 
 def _variant_args(**kw):
@@ -63,19 +60,8 @@ def test_stage1_refuses_the_variant():
 
 def test_attn_desc_struct_matches_header():
     from counting_detr_amd import _ffi
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_attn_desc\s*;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields, ctypes_of = [], {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float"}
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for i, nm in enumerate(decl.split(",")):
-            name = re.findall(r"(\w+)\s*$", nm.strip())[0]
-            ptr = "*" in (decl.split(",")[0] if i == 0 else nm)
-            base = re.match(r"(?:const\s+)?(\w+)", decl).group(1)
-            fields.append((name, "c_void_p" if ptr else ctypes_of[base]))
+    ctypes_of = {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float"}
+    fields = [(name, "c_void_p" if ptr else ctypes_of[base]) for name, base, ptr in abi_header.struct_fields("cdetr_attn_desc")]
     twin = [(n, t.__name__) for n, t in _ffi.AttnDesc._fields_]
     assert twin == fields
     assert "cdetr_attn_fwd" in _ffi.EXPORTS and "cdetr_attn_bwd" in _ffi.EXPORTS

@@ -2,7 +2,6 @@
 what can be checked without a GPU.  The checker is coco_ap's host path (`_evaluate_image`, `average_precision`), which the device path
 leaves untouched.  tests/test_coco_ap_device_gpu.py compares the kernels themselves."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -10,9 +9,8 @@ import pytest
 
 from counting_detr_amd import coco_ap as ca
 
+import abi_header
 import coco_ap_cases as cc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -25,14 +23,11 @@ def L():
 
 def test_entries_exported_and_declared(L):
     from counting_detr_amd import _ffi
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
+    src = abi_header.source()
     for name in ("cdetr_box_iou_xywh", "cdetr_coco_match"):
         assert name in _ffi.EXPORTS and hasattr(L, name)
         assert re.search(r"^int " + name + r"\(", src, flags=re.M), name
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_coco_match_desc\s*;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in body.split(";") if decl.strip() for nm in decl.split(",")]
-    assert names == [f[0] for f in _ffi.CocoMatchDesc._fields_]
+    assert abi_header.field_names("cdetr_coco_match_desc") == [f[0] for f in _ffi.CocoMatchDesc._fields_]
     assert "coco_eval.hip" in __import__("counting_detr_amd.build", fromlist=["SOURCES"]).SOURCES
 
 

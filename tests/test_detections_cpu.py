@@ -4,7 +4,6 @@ come from -- infer.py's literal per-detection loop (through json), coco_ap.refer
 tests/test_detections_gpu.py compares the kernel with the same checker."""
 import ctypes
 import json
-import os
 import re
 
 import numpy as np
@@ -13,9 +12,9 @@ import torch
 
 from counting_detr_amd import coco_ap as ca
 
+import abi_header
 import detections_ref as dr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HWS = [(384, 683), (512, 384), (300, 301), (768, 1024)]
 
 
@@ -141,18 +140,43 @@ def test_store_layout_finish_and_pack_store_order(images):
         store.finish()
 
 
+@pytest.mark.parametrize("cls, args, kw, cuts", [
+    ("DetectionStore", (6, 70), dict(max_det=5), [0, 16, 48, 80, 112, 352, 13792, 14752, 14992]),
+    ("DetectionStore", (3, 257), dict(max_det=100), [0, 16, 32, 48, 64, 2464, 27136, 36736, 39136]),
+    ("DetectionStore", (3, 70), dict(wire_cap=69, eval_cap=69), [0, 16, 32, 48, 64, 624, 2832, 5040, 5600]),
+    ("DetectionStore", (1, 900), {}, [0, 16, 32, 48, 64, 7264, 36064, 64864, 72064]),
+    ("PseudoLabelStore", (6, 533), {}, [0, 16, 48, 80, 112, 4384, 21440, 25712, 42768, 47040]),
+    ("PseudoLabelStore", (2, 10), dict(max_det=4), [0, 16, 32, 48, 64, 128, 448, 528, 784, 848]),
+    ("PseudoLabelStore", (1, 0), {}, [0, 16, 32, 48, 64, 64, 64, 64, 64, 64])])
+def test_store_sections_are_cut_where_they_always_were(cls, args, kw, cuts):
+    """The byte layout of both stores, pinned with literals: [status | counts | wire offsets | eval_off | eval_score | wire | (pair_iou) |
+    eval_boxes | eval_area], every section 16-byte aligned, every member a view of its section, the head zeroed."""
+    from counting_detr_amd import ops
+    s = getattr(ops, cls)(*args, "cpu", **kw)
+    assert s._cuts == cuts and s.buf.numel() == cuts[-1] and s.first == 0 and s._host is None
+    N, E = s.N, s.eval_cap
+    off, W = (s.wire_off, s.wire_cap) if cls == "DetectionStore" else (s.row_off, s.row_cap)
+    assert E == 8 or kw.get("max_det") != 4
+    members = [(s.status, (1,), torch.int32), (s.counts, (N,), torch.int32), (off, (N + 1,), torch.int32), (s.eval_off, (N + 1,), torch.int32),
+               (s.eval_score, (E,), torch.float64), (s.wire, (W, 8), torch.int32)] + \
+              ([(s.pair_iou, (W,), torch.float64)] if cls == "PseudoLabelStore" else []) + \
+              [(s.eval_boxes, (E, 4), torch.float64), (s.eval_area, (E,), torch.float64)]
+    assert len(members) == len(cuts) - 1
+    for k, (t, shape, dt) in enumerate(members):
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous(), k
+        assert t.numel() * t.element_size() <= cuts[k + 1] - cuts[k] and (t.numel() == 0 or t.data_ptr() == s.buf.data_ptr() + cuts[k]), k
+    assert not s.buf[:cuts[4]].any()
+
+
 def test_entry_exported_declared_and_documented(L):
     from counting_detr_amd import _ffi, build
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
+    src = abi_header.source()
     assert "cdetr_emit_detections" in _ffi.EXPORTS and hasattr(L, "cdetr_emit_detections")
     assert re.search(r"^int cdetr_emit_detections\(const cdetr_emit_detections_desc\* d, void\* stream\);", src, flags=re.M)
     assert "detections.hip" in build.SOURCES and L.cdetr_abi_version() == 2
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_emit_detections_desc\s*;", src, flags=re.S).group(1)
-    lines = [ln for ln in body.splitlines() if ln.strip()]
+    lines = [ln for ln in abi_header.struct_body("cdetr_emit_detections_desc").splitlines() if ln.strip()]
     assert all("/*" in ln and "*/" in ln for ln in lines), [ln for ln in lines if "/*" not in ln]      # every field carries its comment
-    bare = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in bare.split(";") if decl.strip() for nm in decl.split(",")]
-    assert names == [f[0] for f in _ffi.EmitDetectionsDesc._fields_]
+    assert abi_header.field_names("cdetr_emit_detections_desc") == [f[0] for f in _ffi.EmitDetectionsDesc._fields_]
     assert ctypes.sizeof(_ffi.EmitDetectionsDesc) == 32 + 12 * 8
 
 

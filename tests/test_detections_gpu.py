@@ -3,6 +3,7 @@ the numpy checker tests/detections_ref.py (pinned to the host path by tests/test
 itself.  Every comparison is array_equal / ==: no tolerance, no case left out."""
 import json
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -173,6 +174,53 @@ def test_undersized_store_raises_and_writes_nothing_out_of_range():
         for k, rec in ((4, 8), (5, 32), (6, 32), (7, 8)):
             assert (raw[c[k] + rec * 70 * fits:c[k + 1]] == 0xA5).all(), (caps, k)
         assert raw[c[1]:c[1] + 12].view(np.int32).tolist() == [70, 70, 70]     # the counts are still the images' own
+
+
+GUARD = 8
+
+
+def guarded_store(N, Q, wire_cap, eval_cap, threshold=0.5, max_det=ca.MAX_DETS):
+    """What emit_detections needs of a DetectionStore, its arrays separate allocations with GUARD sentinel elements behind each."""
+    size = {"status": 1, "counts": N, "wire_off": N + 1, "eval_off": N + 1, "wire": 8 * wire_cap, "eval_boxes": 4 * eval_cap, "eval_area": eval_cap,
+            "eval_score": eval_cap}
+    full = {k: torch.full((n + GUARD,), -777, dtype=torch.float64 if k.startswith("eval_") and k != "eval_off" else torch.int32, device=DEV)
+            for k, n in size.items()}
+    full["status"][0] = full["wire_off"][0] = full["eval_off"][0] = 0
+    s = SimpleNamespace(N=N, Q=Q, threshold=threshold, max_det=max_det, wire_cap=wire_cap, eval_cap=eval_cap, buf=full["status"], full=full, size=size)
+    for k, t in full.items():
+        setattr(s, k, t[:size[k]])
+    s.wire, s.eval_boxes = s.wire.view(-1, 8), s.eval_boxes.view(-1, 4)
+    return s
+
+
+def test_offsets_and_status_after_an_overflow():
+    """Three calls of 3, 3 and 1 images, every query kept, into a store ONE record short of six images: images 0 .. 4 are in place; image 5
+    fits neither section, writes nothing, sets 1 | 2 and leaves its next offsets running past the capacity, unclamped; the third call finds
+    its start beyond the capacity, sets 4, repeats the offsets and writes nothing.  tests/detections_ref.emit_store restates the rule."""
+    rng = np.random.default_rng(10)
+    calls = [batch([dr.make_case(rng, 70, HW3[k], kept="all", ties=1) for k in range(B)]) for B in (3, 3, 1)]
+    cap = 6 * 70 - 1
+    ref = dr.emit_store(calls, 0.5, ca.MAX_DETS, wire_cap=cap, eval_cap=cap)
+    assert ref["placed"] == [(70 * n, 70 * n) for n in range(5)] + [None, None] and ref["status"] == 7
+    assert ref["wire_off"].tolist() == ref["eval_off"].tolist() == [0, 70, 140, 210, 280, 350, 420, 420] and ref["wire_off"][6] == cap + 1
+    s = guarded_store(7, 70, cap, cap)
+    first, words = 0, []
+    for c in calls:
+        ops.emit_detections(T(c[0]), T(c[1]), T(c[2]), T(c[3]), s, first)
+        first += len(c[0])
+        words.append(int(s.status[0]))
+    print("status after each call", words)
+    assert words == [0, 3, 7]
+    for k, t in s.full.items():
+        assert (t[s.size[k]:].cpu() == -777).all(), f"guard words behind {k} changed"
+    assert s.counts.tolist() == ref["counts"].tolist() == [70] * 7
+    assert s.wire_off.tolist() == ref["wire_off"].tolist() and s.eval_off.tolist() == ref["eval_off"].tolist()
+    wire, n = s.wire.cpu().numpy(), 350
+    assert np.array_equal(wire[:n, :7], ref["wire"]) and np.array_equal(wire[:n, 7].view(np.float32), ref["score"]) and len(ref["wire"]) == n
+    for k in ("eval_boxes", "eval_area", "eval_score"):
+        assert np.array_equal(getattr(s, k)[:n].cpu().numpy(), ref[k]), k
+        assert (getattr(s, k)[n:].cpu() == -777).all(), k
+    assert (s.wire[n:].cpu() == -777).all()
 
 
 def _same(a, b):

@@ -2,16 +2,13 @@
 tmp_path, SetCriterion.per_image's CPU composition against the reference's recorded batch-1 losses, and the boundary of the new entry point
 (descriptor mirror, argument checks before any launch)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import eval_split as es
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -90,10 +87,7 @@ def test_per_image_cpu_needs_indices():
 
 def test_descriptor_mirrors_the_header_and_bad_arguments_launch_nothing(lib):
     from counting_detr_amd import _ffi
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_criterion_eval_desc\s*;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in body.split(";") if decl.strip() for nm in decl.strip().split(",")]
+    names = abi_header.field_names("cdetr_criterion_eval_desc")
     assert names == [f[0] for f in _ffi.CriterionEvalDesc._fields_]
     assert not any(n.startswith("g_") or n == "num_boxes" for n in names)                 # forward only, the normaliser is formed in the kernel
     L = lib

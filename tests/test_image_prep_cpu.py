@@ -12,6 +12,7 @@ import pytest
 import torch
 from PIL import Image
 
+import abi_header
 import image_prep_ref as ref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -255,13 +256,10 @@ def L():
 
 def test_entry_exported_and_declared(L):
     from counting_detr_amd import _ffi, build
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
+    src = abi_header.source()
     assert "cdetr_image_prep" in _ffi.EXPORTS and hasattr(L, "cdetr_image_prep")
     assert re.search(r"^int cdetr_image_prep\(const cdetr_image_prep_desc\* d, void\* stream\);", src, flags=re.M)
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_image_prep_desc\s*;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in body.split(";") if decl.strip() for nm in decl.split(",")]
-    assert names == [f[0] for f in _ffi.ImagePrepDesc._fields_]
+    assert abi_header.field_names("cdetr_image_prep_desc") == [f[0] for f in _ffi.ImagePrepDesc._fields_]
     assert "image_prep.hip" in build.SOURCES and L.cdetr_abi_version() == 2
 
 

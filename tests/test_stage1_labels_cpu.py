@@ -17,10 +17,10 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import stage1_labels_ref as ref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 TINY = os.path.join(HERE, "golden", "fsc147_tiny")
 F32 = np.float32
 
@@ -278,13 +278,10 @@ def test_abi_header_struct_and_argument_checks():
     """The descriptor mirrors the header field by field; bad descriptors are refused before any launch (no GPU is touched)."""
     from counting_detr_amd import _ffi
     L = _ffi.lib()
-    src = open(os.path.join(ROOT, "include", "cdetr_hip.h")).read()
+    src = abi_header.source()
     assert "cdetr_emit_pseudo_labels" in _ffi.EXPORTS and hasattr(L, "cdetr_emit_pseudo_labels")
     assert re.search(r"^int cdetr_emit_pseudo_labels\(const cdetr_emit_pseudo_labels_desc\* d, void\* stream\);", src, flags=re.M)
-    body = re.search(r"typedef struct \{([^}]*)\}\s*cdetr_emit_pseudo_labels_desc\s*;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.findall(r"(\w+)\s*$", nm.strip())[0] for decl in body.split(";") if decl.strip() for nm in decl.split(",")]
-    assert names == [f[0] for f in _ffi.EmitPseudoLabelsDesc._fields_]
+    assert abi_header.field_names("cdetr_emit_pseudo_labels_desc") == [f[0] for f in _ffi.EmitPseudoLabelsDesc._fields_]
     assert ctypes.sizeof(_ffi.EmitPseudoLabelsDesc) == 8 * 4 + 14 * 8
     assert "stage1_labels.hip" in __import__("counting_detr_amd.build", fromlist=["SOURCES"]).SOURCES
 
