@@ -100,6 +100,13 @@ def get_args_parser():
     p.add_argument("--device_preprocess", action="store_true",
                    help="the DataLoader workers only decode; resize (PIL-exact), normalisation and padding run on the device in one launch per "
                         "batch (cdetr_image_prep) -- the same image / mask tensors bit for bit")
+    p.add_argument("--eval_every", default=0, type=int,
+                   help="main.py: validate on --split after every N-th epoch and after the last one, on the trainer's own weight images "
+                        "(engine.InferenceEngine(trainer=...): no graph of the trainer or the engine is dropped); the epoch's log line gains "
+                        "test_<k>.  0 = off.  Honours --eval_batch_size / --device_preprocess; --device_detections is the intended combination")
+    p.add_argument("--keep_best", default="mae", choices=["mae", "ap", "loss"],
+                   help="with --eval_every: the epoch whose pass has the lowest MAE / lowest loss / highest AP is also saved to "
+                        "detr_retrain_best.pth (a tie keeps the earlier epoch; ap needs instances_<split>.json)")
     return p
 
 
@@ -173,6 +180,11 @@ def get_args_parser_stage1():
     p.add_argument("--device_labels", action="store_true",
                    help="with --generate_pseudo_label or --test: the labels leave the forward on the device (cdetr_emit_pseudo_labels, one call "
                         "per batch, one copy back per split); the same json byte for byte, the scores read from device memory")
+    p.add_argument("--eval_every", default=0, type=int,
+                   help="validate (the loss of --eval, on the live weights) after every N-th epoch and after the last one; the epoch's line in "
+                        "log.txt gains test_loss / test_loss_wh / test_loss_giou.  0 = off")
+    p.add_argument("--keep_best", default="loss", choices=["loss"],
+                   help="with --eval_every: the epoch with the lowest validation loss is also saved to checkpoint_best.pth")
     return p
 
 

@@ -8,7 +8,8 @@ Three layouts a reference user holds:
     model `AnchorDETR_r50_c5.pth` the shipped script starts from (A2/scripts/var_wh_laplace_600.sh:13): the reference keeps the
     keys that exist in its model except `transformer.pattern.*` and loads them with strict=False;
   * the checkpoints this build's main.py writes: {"model", "optimizer", "lr_scheduler", "epoch", "args"} with the reference's
-    547-key model state dict and torch's own AdamW / StepLR state layouts (engine.Trainer.state_dict).
+    547-key model state dict and torch's own AdamW / StepLR state layouts (engine.Trainer.state_dict); with --eval_every also
+    "best": {"metric", "value", "epoch"} (BestKeeper below) and a copy of the best epoch's checkpoint in detr_retrain_best.pth.
 """
 import torch
 
@@ -91,3 +92,66 @@ def resume_model(model, path_or_ckpt, skip_mismatch=False, log=print):
         log("Skipped (shape mismatch): {}".format(skipped))
     invalidate_caches(model)
     return ckpt, list(missing), skipped
+
+
+# ---------------------------------------------------------------------------------------------------------------- validation inside the run
+def weighted_loss(metrics, weight_dict):
+    """The criterion's weighted total of a validation pass's mean losses: sum_k metrics[k] * weight_dict[k] over the keys both hold, in
+    weight_dict order (the train log's `loss`; the pass logs per-loss means, the total is formed here on the host)."""
+    return sum(float(metrics[k]) * float(w) for k, w in weight_dict.items() if k in metrics)
+
+
+def epoch_log_line(train_stats, test_stats, epoch, **extra):
+    """One epoch's json log entry in the reference's (commented-out) format: `train_<k>` for every training statistic, then `test_<k>` for
+    every number of the epoch's validation pass (none when the epoch had no pass: `test_stats` None), then "epoch" and whatever else
+    the driver logs behind it."""
+    line = {f"train_{k}": v for k, v in train_stats.items()}
+    if test_stats is not None:
+        line.update({f"test_{k}": v for k, v in test_stats.items()})
+    line["epoch"] = epoch
+    line.update(extra)
+    return line
+
+
+def validation_due(epoch, every, epochs):
+    """Whether epoch `epoch` (0-based) of a run to `epochs` ends with a validation pass: every `every`-th epoch and always the last one;
+    `every` 0 = never."""
+    return every > 0 and ((epoch + 1) % every == 0 or epoch + 1 == epochs)
+
+
+class BestKeeper:
+    """Which epoch's validation pass was the best so far (--keep_best).  "mae" and "loss" improve downwards, "ap" upwards; only a strict
+    improvement counts, so a tie keeps the earlier epoch, and a NaN (or a missing number) never becomes best.  `state()` is the
+    checkpoint's "best" entry, `load()` reads it back: a resumed run never takes a worse pass for the best.  Plain Python, no device."""
+    METRICS = {"mae": ("MAE", False), "ap": ("AP", True), "loss": ("loss", False)}
+
+    def __init__(self, metric="mae", has_ground_truth=True):
+        if metric not in self.METRICS:
+            raise ValueError(f"--keep_best {metric}: choose from {sorted(self.METRICS)}")
+        if metric == "ap" and not has_ground_truth:
+            raise ValueError("--keep_best ap needs the split's box ground truth (instances_<split>.json): it is not there")
+        self.metric = metric
+        self.key, self.higher = self.METRICS[metric]
+        self.value, self.epoch = None, None
+
+    def update(self, stats, epoch):
+        """-> True when this pass's number is better than every earlier one (the caller then writes the best checkpoint)."""
+        v = (stats or {}).get(self.key)
+        if v is None:
+            return False
+        v = float(v)
+        if v != v:
+            return False
+        if self.value is not None and not (v > self.value if self.higher else v < self.value):
+            return False
+        self.value, self.epoch = v, int(epoch)
+        return True
+
+    def state(self):
+        return {"metric": self.metric, "value": self.value, "epoch": self.epoch}
+
+    def load(self, state):
+        """Take over a checkpoint's "best" entry; one of another metric (or none) leaves the keeper empty.  -> self."""
+        if state and state.get("metric") == self.metric and state.get("value") is not None:
+            self.value, self.epoch = float(state["value"]), state.get("epoch")
+        return self

@@ -882,8 +882,8 @@ class Trainer:
         InferenceEngine built on the same model) calls this.
         Cost: a device synchronisation now, then one re-capture (~0.1 s) per (shape, capacity) key the loop meets again and a
         rebuilt weight mirror.  Building or refreshing an InferenceEngine on the model BEING TRAINED (a periodic evaluation) therefore costs
-        the trainer its whole cache once per evaluation: correct, ~0.1 s x the number of keys -- evaluate at epoch boundaries (main.py does),
-        not every few steps."""
+        the trainer its whole cache once per evaluation: correct, ~0.1 s x the number of keys -- a periodic evaluation uses
+        InferenceEngine(model, trainer=self) instead, which rides on this trainer's weight images and invalidates nothing (main.py --eval_every)."""
         if self._cache or self._entry is not None or self._frozen:
             if self.flat_g.is_cuda:
                 torch.cuda.synchronize()
@@ -1808,10 +1808,24 @@ class InferenceEngine:
     stage (stem + max-pool + layer1, throughput-bound) runs on a side stream beside this call's latency-bound encoder / decoder -- released
     by a signal kernel that the captured forward carries right behind its backbone.  Measured (profiles/r4_inference_prefetch.txt): 2.5 %
     SLOWER than the plain linear graph (510 vs 522 img/s at 800x800, 787 vs 812 at 384x576) -- the inference forward has no window like the
-    training step's Hungarian solve, the flood only stretches the encoder / decoder chain -- so it is OFF by default; bit-identical either way."""
+    training step's Hungarian solve, the flood only stretches the encoder / decoder chain -- so it is OFF by default; bit-identical either way.
+    `trainer=` (validation inside a training run): the engine RIDES on an engine.Trainer of the same model.  It builds no images of its own and
+    never calls checkpoint.invalidate_caches -- `engine.mirror` is `trainer.mirror`, whose forward images the trainer rewrites every step at
+    fixed addresses; `sync()` rewrites them once more behind the epoch's last optimizer step, before a pass's first forward.  Nothing the
+    captured forwards point at (those images, the FrozenBN folds, the stem images: frozen layers) moves in training, so the engine's graphs
+    AND the trainer's survive from epoch to epoch.  A trainer mirror of a new identity (a real invalidation) drops this engine's graphs.
+    Its arithmetic is the trainer's forward arithmetic; calls raise while the trainer's mirror scope is armed (inside a step)."""
 
-    def __init__(self, model, threshold=0.5, graphs=True, max_graphs=48, device=None, precision=None, prefetch=False):
+    def __init__(self, model, threshold=0.5, graphs=True, max_graphs=48, device=None, precision=None, prefetch=False, trainer=None):
         from . import ops as _ops
+        self.trainer = trainer
+        if trainer is not None:                 # a riding engine: the trainer's weight images and forward arithmetic (class docstring)
+            if trainer.model is not model:
+                raise ValueError("InferenceEngine(trainer=...): the trainer trains another model than the one passed")
+            if precision is not None and int(precision) != trainer.arith[0]:
+                raise ValueError(f"InferenceEngine(trainer=...): precision {precision} is not the trainer's forward arithmetic {trainer.arith[0]}")
+            precision = trainer.arith[0]
+        self._mirror_seen = None                # riding: the trainer's mirror this engine's graphs were captured against
         self.arith = (int(_ops.PRECISION if precision is None else precision), int(_ops.PRECISION_BWD))      # (ops.arithmetic: this engine's own)
         self.model, self.threshold, self.graphs, self.max_graphs = model, threshold, graphs, max_graphs
         p0 = next(model.parameters(), None)
@@ -1826,22 +1840,37 @@ class InferenceEngine:
         self._frozen, self._pf_stream, self._pf_pool, self._sig = {}, None, None, None
         self.stats = {"captures": 0, "calls": 0, "prefetch_hits": 0}
         import weakref
-        model.__dict__.setdefault("_graph_cache_owners", []).append(weakref.ref(self))
-        self.refresh_weights()
+        model.__dict__.setdefault("_graph_cache_owners", []).append(weakref.ref(self))      # (riding too: a real invalidation reaches it)
+        if trainer is None:
+            self.refresh_weights()
 
     def clear_graph_cache(self):
         if self._cache or self._frozen:
             if self.device.type == "cuda":
                 torch.cuda.synchronize()
-            self._cache.clear()
-            self._frozen.clear()
+            self._drop_graphs()
         self._mirror_stale = True
+
+    def _drop_graphs(self):
+        """Every captured forward and frozen-stage graph goes, and the pool handles with them: a graph memory pool whose last graph has been
+        destroyed cannot be captured into again (the caching allocator asserts on its use count), the next capture opens a new one."""
+        self._cache.clear()
+        self._frozen.clear()
+        self._pool = self._pf_pool = None
 
     @property
     def mirror(self):
         """Forward weight images, rebuilt after every invalidation of the FrozenBN folds (see Trainer.mirror: lookups are keyed on the folds'
         addresses).  Until round 5 this engine built its images BEFORE refresh_weights() invalidated the folds: every backbone lookup missed and
         the forward ran on the fp32 weights + scale vectors -- correct, slower."""
+        if self.trainer is not None:
+            # riding: the trainer's images, read at every call.  A mirror of another identity means the trainer rebuilt it after a real
+            # invalidation (checkpoint load, sync_replicas): this engine's graphs hold the old one's addresses
+            m = self.trainer.mirror
+            if m is not self._mirror_seen:
+                self.clear_graph_cache()
+                self._mirror_seen = m           # (nothing is rewritten here: a rebuilt mirror starts empty until the next sync() / trainer step)
+            return m
         if self._mirror_stale:
             has = self.device.type == "cuda" and next(self.model.parameters(), None) is not None
             self._mirror = build_weight_mirror(self.model, self._named, dgrad=False) if has else None
@@ -1852,13 +1881,32 @@ class InferenceEngine:
 
     @_scoped
     def refresh_weights(self):
-        """Call after loading / changing the model's weights: rebuilds the forward weight images (and drops the graphs' cached folds)."""
+        """Call after loading / changing the model's weights: rebuilds the forward weight images (and drops the graphs' cached folds).
+        A riding engine (trainer=...) invalidates nothing and owns no images: `sync()`."""
+        if self.trainer is not None:
+            return self.sync()
         from .checkpoint import invalidate_caches
         invalidate_caches(self.model)
         if self.mirror is not None:
             self.mirror.refresh("fwd")
-        self._cache.clear()
-        self._frozen.clear()
+        self._drop_graphs()
+
+    def _check_disarmed(self):
+        """A riding engine's `with ops.scope(MIRROR=...)` blocks must not open inside the trainer's armed mirror scope (forward .. last piece of
+        the backward): scopes restore in LIFO order, the trainer's later exit would put this engine's stale value back."""
+        if self.trainer is not None and getattr(self.trainer, "_mscope", None) is not None:
+            raise RuntimeError("InferenceEngine(trainer=...): the trainer is inside a step (its weight-mirror scope is armed); validate between steps")
+
+    def sync(self):
+        """Riding engine: bring the trainer's forward weight images up to the current weights (ONE cdetr_weight_images launch).  The optimizer
+        step that ends an epoch changes the weights AFTER that step's forward refreshed the images: call this before the first forward of
+        every validation pass, or the pass runs on weights one step old.  Without a trainer: the images are this engine's own, rewritten."""
+        from . import ops
+        self._check_disarmed()
+        with ops.arithmetic(*self.arith):
+            m = self.mirror
+            if m is not None:
+                m.refresh("fwd")
 
     @torch.no_grad()
     def _run(self, images, mask, rects):
@@ -1882,8 +1930,9 @@ class InferenceEngine:
         h, w = body.frozen_out_hw(H, W)
         if self._pf_stream is None:
             self._pf_stream, _ = probe_side_stream(torch.cuda.current_stream(), self.device)
-            self._pf_pool = torch.cuda.graph_pool_handle()
             self._sig = torch.zeros(2, dtype=torch.int32, device=self.device)
+        if self._pf_pool is None:
+            self._pf_pool = torch.cuda.graph_pool_handle()
         ps = self._pf_stream
         fs = {"images": torch.zeros(shape, device=self.device), "x": torch.empty((B, h, w, 256), device=self.device),
               "xs": torch.empty((B, h, w, 256), device=self.device), "token": None, "keep": None}
@@ -1907,6 +1956,9 @@ class InferenceEngine:
         nt = samples if hasattr(samples, "decompose") else nested_tensor_from_tensor_list(samples)
         images, mask = nt.decompose()
         self.stats["calls"] += 1
+        if self.trainer is not None:
+            self._check_disarmed()
+            _ = self.mirror                        # a rebuilt trainer mirror drops the graphs BEFORE the lookup below
         if not self.graphs or not images.is_cuda:
             return self._run(images, mask, rects)
         body = self.model.backbone.body if self._prefetch_on else None

@@ -38,20 +38,29 @@ from counting_detr_amd.misc import NestedTensor
 
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False):
+          per_image=False, engine=None, write_json=True):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
     (the split's instances json) the metrics also carry the box AP, matched from the device-resident detections.
     `per_image` (--eval_batch_size > 1): the loader yields batches of several images of one size; the losses are `criterion.per_image`'s, one
-    value per image, summed image by image -- what the batch-1 loop logs."""
-    output_path = os.path.join(output_dir, "predictions_" + split + ".json")
-    if os.path.isfile(output_path):
+    value per image, summed image by image -- what the batch-1 loop logs.
+    `engine`: an InferenceEngine of `model` made by the caller instead of a new one per call (main.py --eval_every: one engine riding on the
+    trainer, engine.InferenceEngine(trainer=...), its captured forwards reused pass after pass; its weight images are brought up to date
+    here, `engine.sync()`, before the first forward).  `write_json=False`: no predictions file is written or removed (the device path then
+    returns None for the predictions dict instead of building it); the metrics are the same either way."""
+    output_path = os.path.join(output_dir, "predictions_" + split + ".json") if write_json else None
+    if output_path is not None and os.path.isfile(output_path):
         os.remove(output_path)
     model.eval()
     criterion.eval()
-    from counting_detr_amd.engine import InferenceEngine
-    engine = InferenceEngine(model, threshold, graphs=graphs and torch.device(device).type == "cuda", device=device)
+    if engine is None:
+        from counting_detr_amd.engine import InferenceEngine
+        engine = InferenceEngine(model, threshold, graphs=graphs and torch.device(device).type == "cuda", device=device)
+    elif engine.model is not model or engine.threshold != threshold:
+        raise ValueError("infer: the engine passed in was built for another model or threshold")
+    elif getattr(engine, "trainer", None) is not None:
+        engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
         return _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image)
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
@@ -100,8 +109,9 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
             pred_counts.append(int(kb.sum()))
             gt_counts.append(int(targets[b]["boxes"].shape[0]))
             n_img += 1
-    with open(output_path, "w") as handle:
-        json.dump(predictions, handle)
+    if output_path is not None:
+        with open(output_path, "w") as handle:
+            json.dump(predictions, handle)
     metrics = {k: v / max(n_img, 1) for k, v in loss_sum.items()}
     if n_img:       # images without objects contribute to MAE / RMSE only (the reference divides by the count, A2/eval_all.py:264-265)
         metrics.update(counting_metrics(pred_counts, gt_counts))
@@ -176,14 +186,18 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
                     loss_sum[k] = loss_sum.get(k, 0.0) + v * n_t
             pred_counts = host["counts"].tolist()
             image_ids = [m[2] for m in meta_h]
+        if n_img and output_path is not None:
             per_image = np.diff(host["wire_off"]).tolist()
             ann_image = [i for i, c in zip(image_ids, per_image) for _ in range(c)]
             wire, score = host["wire"].tolist(), host["score"].astype(np.float64).tolist()
             predictions["annotations"] = [{"id": k + 1, "image_id": i, "area": w[4], "bbox": w[:4], "category_id": 1, "score": sc, "point": w[5:7]}
                                           for k, (i, w, sc) in enumerate(zip(ann_image, wire, score))]
             predictions["images"] = [{"id": m[2], "height": m[0], "width": m[1], "file_name": "None"} for m in meta_h]
-        with open(output_path, "w") as handle:
-            json.dump(predictions, handle)
+        if output_path is not None:
+            with open(output_path, "w") as handle:
+                json.dump(predictions, handle)
+        else:
+            predictions = None
         metrics = {k: v / max(n_img, 1) for k, v in loss_sum.items()}
         if n_img:
             metrics.update(counting_metrics(pred_counts, gt_counts))
@@ -226,6 +240,24 @@ def eval_loader(args, device):
     return dl, B > 1
 
 
+def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, write_json=True):
+    """One pass over `dl` (eval_loader) -> the metrics this file prints: mean losses, MAE / RMSE / NAE / SRE, `images`, and the six AP numbers
+    when the split's instances json is there.  `engine` / `write_json`: see `infer` (main.py --eval_every passes its riding engine); the
+    file is written regardless when the AP has to be read back from it (no --device_detections, or --ap_on_host)."""
+    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+    on_device = bool(getattr(args, "device_detections", False))
+    ap_in_loop = on_device and os.path.isfile(gt_json) and not getattr(args, "ap_on_host", False)      # matched from the device-resident detections
+    ap_from_file = os.path.isfile(gt_json) and not ap_in_loop
+    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
+                       gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file)
+    if ap_from_file:
+        from counting_detr_amd.coco_ap import ap_from_json
+        # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
+        ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None
+        metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
+    return metrics
+
+
 def main(args):
     device = torch.device(args.device)
     model, criterion, _ = counting_detr_amd.build_model(args)
@@ -235,16 +267,7 @@ def main(args):
         model.load_state_dict(ckpt["model"], strict=True)
     dl, per_image = eval_loader(args, device)
     os.makedirs(args.output_dir, exist_ok=True)
-    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
-    on_device = bool(getattr(args, "device_detections", False))
-    ap_in_loop = on_device and os.path.isfile(gt_json) and not getattr(args, "ap_on_host", False)      # matched from the device-resident detections
-    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
-                       gt_json=gt_json if ap_in_loop else None, per_image=per_image)
-    if os.path.isfile(gt_json) and not ap_in_loop:
-        from counting_detr_amd.coco_ap import ap_from_json
-        # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
-        ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None
-        metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
+    metrics = evaluate_split(model, criterion, dl, per_image, device, args)
     print(json.dumps(metrics))
     with open(os.path.join(args.output_dir, "results_" + args.split + ".txt"), "w") as f:
         f.write(json.dumps(metrics) + "\n")

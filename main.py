@@ -8,6 +8,9 @@ Differences: any number of images per GPU (--images_per_gpu), data-parallel over
 DataLoader yielding the reference's sample dicts to `train_one_epoch`).  Without --synthetic the FSC-147 reader of
 counting_detr_amd/data.py feeds the step (batched collate + pinned-memory prefetch); with --device_preprocess the workers only decode
 and the resize / normalisation / padding of a batch is one launch on the prefetch stream (same tensors bit for bit).
+--eval_every N: the validation call the reference left commented out (A2/main.py "Evaluate ...").  After every N-th epoch and the last one rank 0
+walks --split through infer.py's loop on the live weights (an InferenceEngine riding on the trainer: no graph is dropped on either side), the
+epoch's log line gains test_<k>, and --keep_best {mae,ap,loss} also saves the best epoch to detr_retrain_best.pth ("best" in every checkpoint).
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --synthetic --no_aux_loss ...
@@ -50,6 +53,27 @@ class SyntheticLoader:
         return self.steps
 
 
+class Validator:
+    """--eval_every: one pass over --split (infer.py's loop and metrics) on the weights as they stand, between two epochs.  The engine rides on
+    the trainer (engine.InferenceEngine(trainer=...)): the trainer's forward weight images, nothing invalidated -- the trainer's captured
+    steps and the engine's captured forwards both live on from pass to pass.  Engine and loader are built once."""
+
+    def __init__(self, trainer, criterion, args, device):
+        import infer as _infer
+        from counting_detr_amd.engine import InferenceEngine
+        self._infer, self.trainer, self.criterion, self.args, self.device = _infer, trainer, criterion, args, device
+        self.loader, self.per_image = _infer.eval_loader(args, device)
+        self.engine = InferenceEngine(trainer.model, graphs=device.type == "cuda", device=device, trainer=trainer)
+
+    def run(self, write_json=True):
+        try:
+            return self._infer.evaluate_split(self.trainer.model, self.criterion, self.loader, self.per_image, self.device, self.args,
+                                              engine=self.engine, write_json=write_json)
+        finally:
+            self.trainer.model.train()
+            self.criterion.train()
+
+
 def main(args):
     utils.init_distributed_mode(args)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -84,6 +108,14 @@ def main(args):
         if resumed > args.start_epoch:
             print(f"resume: optimizer state restored, continuing at epoch {resumed} (checkpoint epoch {resumed - 1})")
             args.start_epoch = resumed
+    # --eval_every: validation inside the run, on the trainer's own weight images (engine.InferenceEngine(trainer=...)), + the best checkpoint
+    keeper = validator = last_metrics = None
+    if args.eval_every > 0:
+        if args.synthetic:
+            raise SystemExit("--eval_every validates on a dataset split: not with --synthetic")
+        keeper = ckpt_io.BestKeeper(args.keep_best, os.path.isfile(os.path.join(args.data_path, "instances_" + args.split + ".json")))
+        if checkpoint is not None and (args.resume_optimizer or args.auto_resume):
+            keeper.load(checkpoint.get("best"))           # a resumed run never overwrites a better detr_retrain_best.pth with a worse one
     if args.start_epoch >= args.epochs:
         print(f"nothing to train: start epoch {args.start_epoch} >= --epochs {args.epochs}")
     torch.manual_seed(args.seed + 1 + utils.get_rank())                 # data-side RNG (synthetic batches, augmentation)
@@ -110,16 +142,31 @@ def main(args):
         paths = [output_dir / "detr_retrain.pth"]
         if (epoch + 1) % args.lr_drop == 0 or (epoch + 1) % 10 == 0:
             paths.append(output_dir / f"detr_retrain_{epoch:04}.pth")
+        test_stats = None
+        if keeper is not None and ckpt_io.validation_due(epoch, args.eval_every, args.epochs):
+            if utils.is_main_process():        # rank 0 validates (the whole split), the other ranks wait in the barrier below
+                if validator is None:          # built once: the engine's captured forwards and the loader serve every later pass
+                    validator = Validator(trainer, criterion, args, device)
+                last_metrics = validator.run(write_json=epoch + 1 == args.epochs)      # the run leaves the last pass's predictions file
+                test_stats = {"loss": ckpt_io.weighted_loss(last_metrics, criterion.weight_dict), **last_metrics}
+                if keeper.update(test_stats, epoch):
+                    paths.append(output_dir / "detr_retrain_best.pth")
+            if utils.is_dist_avail_and_initialized():
+                torch.distributed.barrier()
         if utils.is_main_process():            # only rank 0 pays for the host copy of the moments
             ckpt = {"model": model.state_dict(), "optimizer": trainer.state_dict(), "lr_scheduler": trainer.lr_scheduler_state_dict(),
                     "epoch": epoch, "args": args}
+            if keeper is not None:
+                ckpt["best"] = keeper.state()
             for p in paths:
                 torch.save(ckpt, p)
         if utils.is_main_process():
             with (output_dir / "detr_retrain.txt").open("a") as f:
-                f.write(json.dumps({**{f"train_{k}": v for k, v in stats.items()}, "epoch": epoch}) + "\n")
+                f.write(json.dumps(ckpt_io.epoch_log_line(stats, test_stats, epoch)) + "\n")
     print("time: ", time.time() - start)
-    if args.eval and not args.synthetic:                                # counting evaluation on the validation split (A2/infer.py)
+    if args.eval and last_metrics is not None:                          # --eval_every already ran this pass after the last epoch
+        print("counting metrics ({}): {}".format(args.split, json.dumps(last_metrics)))
+    elif args.eval and not args.synthetic:                              # counting evaluation on the validation split (A2/infer.py)
         if utils.is_main_process():
             import infer as _infer
             dl, per_image = _infer.eval_loader(args, device)           # --eval_batch_size: batches of one resized size, per-image losses

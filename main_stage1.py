@@ -14,6 +14,9 @@ and every 10 epochs), one JSON line per epoch in log.txt.
                            outputs["pred_boxes"] through a PostProcess the 1st-stage model does not feed: not reproduced)
   --device_labels          with either of the two: one cdetr_emit_pseudo_labels call per batch instead of the per-annotation host loop, one
                            copy back per split, the scores straight from device memory; the same files byte for byte
+  --eval_every N           the validation loss of --eval after every N-th epoch and after the last, on the live weights: test_loss /
+                           test_loss_wh / test_loss_giou in the epoch's log line; the epoch with the lowest loss is also saved to
+                           checkpoint_best.pth and every checkpoint carries "best" = {"metric", "value", "epoch"} (--keep_best loss)
   --auto_resume            continue from <output_dir>/checkpoint.pth: weights, AdamW moments, StepLR state and the next epoch
   --synthetic              seeded batches, no dataset
   --ragged_batches         batches may mix images with different numbers of points (padded to the batch maximum, per-image counts read by
@@ -176,6 +179,14 @@ def main(args):
         if resumed > args.start_epoch:
             print(f"resume: optimizer state restored, continuing at epoch {resumed}")
             args.start_epoch = resumed
+    keeper = val_loader = None
+    if args.eval_every > 0:                    # the loss of --eval on the live weights, between epochs (+ checkpoint_best.pth)
+        if args.synthetic:
+            raise SystemExit("--eval_every validates on the val split: not with --synthetic")
+        keeper = ckpt_io.BestKeeper(args.keep_best)
+        if checkpoint is not None and args.auto_resume:
+            keeper.load(checkpoint.get("best"))
+        val_loader = loader_for(args, "val", device=device)       # the loader --eval builds (--ragged_batches honoured), built once
     torch.manual_seed(args.seed + 1)
     n_parameters = sum(p.numel() for p in model.parameters() if p.requires_grad)
     print("Start training")
@@ -190,12 +201,20 @@ def main(args):
         paths = [output_dir / "checkpoint.pth"]
         if (epoch + 1) % args.lr_drop == 0 or (epoch + 1) % 10 == 0:
             paths.append(output_dir / f"checkpoint{epoch:04}.pth")
+        test_stats = None
+        if keeper is not None and ckpt_io.validation_due(epoch, args.eval_every, args.epochs):
+            # eager, no weight mirror in force, nothing invalidated: the trainer's captured steps stay (evaluate leaves the model in train mode)
+            test_stats = {k: v for k, v in evaluate(model, criterion, val_loader, device).items() if k.startswith("loss")}
+            if keeper.update(test_stats, epoch):
+                paths.append(output_dir / "checkpoint_best.pth")
         ckpt = {"model": model.state_dict(), "optimizer": trainer.state_dict(), "lr_scheduler": trainer.lr_scheduler_state_dict(),
                 "epoch": epoch, "args": args}
+        if keeper is not None:
+            ckpt["best"] = keeper.state()
         for p in paths:
             torch.save(ckpt, p)
         with (output_dir / "log.txt").open("a") as f:
-            f.write(json.dumps({**{f"train_{k}": v for k, v in stats.items()}, "epoch": epoch, "n_parameters": n_parameters}) + "\n")
+            f.write(json.dumps(ckpt_io.epoch_log_line(stats, test_stats, epoch, n_parameters=n_parameters)) + "\n")
     print("Training time {:.1f} s".format(time.time() - start))
 
 
