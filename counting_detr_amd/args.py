@@ -107,7 +107,24 @@ def get_args_parser():
     p.add_argument("--keep_best", default="mae", choices=["mae", "ap", "loss"],
                    help="with --eval_every: the epoch whose pass has the lowest MAE / lowest loss / highest AP is also saved to "
                         "detr_retrain_best.pth (a tie keeps the earlier epoch; ap needs instances_<split>.json)")
+    # the three flags below leave NO attribute behind when they are not given (argparse.SUPPRESS): a run without them sees the namespace -- and
+    # writes the checkpoint's "args" -- it always did; readers use getattr(args, name, default), threshold 0.5 and no sweep being the defaults
+    p.add_argument("--threshold", default=argparse.SUPPRESS, type=_threshold,
+                   help="infer.py / main.py --eval / --eval_every: a query counts (and becomes a detection) when the fp32 sigmoid(logit) >= "
+                        "float32(T); default 0.5.  infer.py also takes `ckpt`: the calibrated threshold the --resume checkpoint carries")
+    p.add_argument("--sweep_thresholds", default=argparse.SUPPRESS, type=str, metavar="SPEC",
+                   help="infer.py / main.py --eval / --eval_every: also report counts and AP at these thresholds from the same pass, into "
+                        "threshold_sweep_<split>.json.  SPEC = lo:hi:n (n evenly spaced values, both ends) or a comma list; at most 32 distinct "
+                        "fp32 values, --threshold included.  With --device_detections: one cdetr_count_sweep launch per batch, one matching per split")
+    p.add_argument("--calibrate_threshold", default=argparse.SUPPRESS, choices=["mae", "rmse", "nae", "sre", "ap"],
+                   help="main.py with --eval_every and --sweep_thresholds: the sweep's best threshold for this metric goes into the epoch's log "
+                        "line (test_best_threshold, test_best_<metric>) and into every checkpoint written afterwards (count_threshold)")
     return p
+
+
+def _threshold(text):
+    """--threshold: a number, or `ckpt`."""
+    return "ckpt" if text == "ckpt" else float(text)
 
 
 def get_args_parser_stage1():

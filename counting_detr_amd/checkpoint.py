@@ -9,7 +9,10 @@ Three layouts a reference user holds:
     keys that exist in its model except `transformer.pattern.*` and loads them with strict=False;
   * the checkpoints this build's main.py writes: {"model", "optimizer", "lr_scheduler", "epoch", "args"} with the reference's
     547-key model state dict and torch's own AdamW / StepLR state layouts (engine.Trainer.state_dict); with --eval_every also
-    "best": {"metric", "value", "epoch"} (BestKeeper below) and a copy of the best epoch's checkpoint in detr_retrain_best.pth.
+    "best": {"metric", "value", "epoch"} (BestKeeper below) and a copy of the best epoch's checkpoint in detr_retrain_best.pth; after a
+    pass calibrated with --calibrate_threshold also "count_threshold": {"metric", "threshold", "value", "epoch"}
+    (threshold_sweep.calibration writes it, threshold_sweep.checkpoint_threshold reads it for `infer.py --threshold ckpt`).  A checkpoint
+    without either entry loads exactly as before.
 """
 import torch
 

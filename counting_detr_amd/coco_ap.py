@@ -30,6 +30,11 @@ order as the loops of `average_precision`, so the two paths return EQUAL numbers
 STORE PATH (`summarize_store`): the detections never visit the host as dicts -- cdetr_emit_detections (csrc/detections.hip) left them in an
 ops.DetectionStore in evaluation order, `pack_store` packs only the ground truths and `match_on_device` reads the detections from device memory;
 the same launch, the same `accumulate`, EQUAL numbers again (tests/test_detections_gpu.py).
+
+SCORE-THRESHOLD SWEEP (`summarize_store_sweep`, infer.py --sweep_thresholds): the six numbers at several score thresholds from ONE matching at
+the lowest of them -- in evaluation order the detections a higher threshold keeps are a prefix, per image and after the merge, and a greedy
+match never looks ahead (`accumulate_sweep`).  `summarize_sweep` filters and evaluates once per threshold on the host: slow,
+and the checker (tests/test_threshold_sweep_cpu.py, _gpu.py).
 """
 import json
 
@@ -140,18 +145,30 @@ def accumulate(scores, matched, ignored, npig):
     """The tail of `average_precision` as array operations: all images' detections (scores [N], flags [T, N], images concatenated in
     `pack_images` order) merged by descending score (stable), cumulative tp / fp, precision envelope = running maximum from the right,
     sampled at the 101 recall thresholds.  Same float64 operations in the same order as the loops there: the result is EQUAL, not close."""
-    T, R = len(IOU_THRS), len(REC_THRS)
     if npig == 0:
-        return -np.ones((T, R))
-    precision = np.zeros((T, R))
-    order = np.argsort(-np.asarray(scores, dtype=np.float64), kind="mergesort")
+        return -np.ones((len(IOU_THRS), len(REC_THRS)))
+    return _sample(*_merged_cumulative(scores, matched, ignored)[1:], npig)
+
+
+def _merged_cumulative(scores, matched, ignored):
+    """The head of `accumulate`: -> (scores in merged order [N], cumulative tp [T, N], cumulative fp [T, N]), float64.  The sums count flags, so
+    a column prefix of them IS the cumulative sum of that prefix of the merged list (`accumulate_sweep`)."""
+    T = len(IOU_THRS)
+    scores = np.asarray(scores, dtype=np.float64)
+    order = np.argsort(-scores, kind="mergesort")
     matched = np.asarray(matched, dtype=bool).reshape(T, -1)[:, order]
     ignored = np.asarray(ignored, dtype=bool).reshape(T, -1)[:, order]
-    N = matched.shape[1]
+    return (scores[order], np.cumsum(matched & ~ignored, axis=1, dtype=np.float64), np.cumsum(~matched & ~ignored, axis=1, dtype=np.float64))
+
+
+def _sample(tps, fps, npig):
+    """The tail of `accumulate`, shared with `accumulate_sweep`: cumulative tp / fp [T, N] of a merged list and its npig > 0 -> precision
+    [T, R]: recall and precision, the envelope from the right, the 101-point sampling (zeros for an empty list)."""
+    T, R = len(IOU_THRS), len(REC_THRS)
+    precision = np.zeros((T, R))
+    N = tps.shape[1]
     if N == 0:
         return precision
-    tps = np.cumsum(matched & ~ignored, axis=1, dtype=np.float64)
-    fps = np.cumsum(~matched & ~ignored, axis=1, dtype=np.float64)
     rc = tps / npig
     pr = tps / (fps + tps + np.spacing(1))
     pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]
@@ -312,6 +329,60 @@ def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS):
     matched, ignored, npig = match_on_device(pack, device, areas)
     by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(areas)}
     return _six(by_area)
+
+
+def accumulate_sweep(scores, matched, ignored, npig, thresholds):
+    """`accumulate` for every score threshold of `thresholds` from the flags of ONE matching at (or below) the lowest of them -> a list of
+    precision [T, R].  In evaluation order the detections kept at threshold t are a prefix of every image's list (descending score, cut at
+    max_det: min(count_t, max_det) of them), the greedy matching gives detection k flags that depend on the detections before it only, and
+    the stable merge by score keeps the kept ones a prefix again: the first n_t = #{score >= float32(t)} columns of the cumulative sums.
+    Only the envelope and the sampling (`_sample`) run per threshold."""
+    if npig == 0:
+        return [-np.ones((len(IOU_THRS), len(REC_THRS))) for _ in thresholds]
+    merged, tps, fps = _merged_cumulative(scores, matched, ignored)
+    s32 = merged.astype(np.float32)                     # the scores are fp32 probabilities widened: the cast is exact
+    out = []
+    for t in thresholds:
+        n_t = int((s32 >= np.float32(t)).sum())
+        if n_t and not (s32[:n_t] >= np.float32(t)).all():
+            raise RuntimeError("coco_ap: the detections kept at a threshold are not a prefix of the merged list (NaN scores?)")
+        out.append(_sample(tps[:, :n_t], fps[:, :n_t], npig))
+    return out
+
+
+def summarize_sweep(gt_by_img, dt_by_img, thresholds, max_det=MAX_DETS):
+    """The six numbers per score threshold on the host, the slow and obvious way (the checker of `summarize_store_sweep`): `summarize` on
+    the detections with float32(score) >= float32(t), once per threshold.  -> list of dicts, in the order of `thresholds`."""
+    out = []
+    for t in thresholds:
+        t32 = np.float32(t)
+        kept = {i: [d for d in dl if np.float32(d["score"]) >= t32] for i, dl in dt_by_img.items()}
+        out.append(summarize(gt_by_img, kept, max_det=max_det))
+    return out
+
+
+def summarize_flags_sweep(scores, flags, thresholds):
+    """The prefix route's summary: `flags` = {area: (matched [T, D], det_ignored [T, D], npig)} of one matching at the lowest threshold,
+    `scores` [D] in the same (images concatenated) order -> the six numbers per threshold."""
+    per_area = {a: accumulate_sweep(scores, m, ig, int(n), thresholds) for a, (m, ig, n) in flags.items()}
+    return [_six({a: per_area[a][k] for a in per_area}) for k in range(len(thresholds))]
+
+
+def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS):
+    """`summarize_store` at every score threshold of `thresholds` from ONE cdetr_coco_match launch: the store was emitted at the lowest
+    threshold (checked), the flags of every higher one are a prefix of what that launch returns (`accumulate_sweep`).  -> list of the six
+    numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold."""
+    t32 = np.asarray(list(thresholds), dtype=np.float64).astype(np.float32)
+    if len(t32) == 0 or np.isnan(t32).any() or np.float32(store.threshold) != t32.min():
+        raise RuntimeError(f"coco_ap: a sweep over {t32.tolist()} needs a store emitted at its lowest threshold, this one was emitted at "
+                           f"{store.threshold}")
+    if store.max_det != max_det:
+        raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
+    device = store.buf.device if device is None else _cuda(device)
+    pack = pack_store(gt_by_img, store, image_ids)
+    areas = tuple(AREA_RNG)
+    matched, ignored, npig = match_on_device(pack, device, areas)
+    return summarize_flags_sweep(pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(areas)}, t32)
 
 
 def gt_from_json(gt_json, ids):

@@ -2226,6 +2226,56 @@ class PseudoLabelStore(_RecordStore):
         self._cut(device)
 
 
+def count_sweep(prob, thresholds, table, first, events=None):
+    """cdetr_count_sweep: table[first + b, t] = #{q : prob[b, q] >= thresholds[t]} for the B images of one forwarded batch.  Device tensors:
+    prob fp32 [B, Q] (the counting rule's own sigmoid), thresholds fp32 [T] ASCENDING (1 <= T <= 32), table int32 [N, T] contiguous (the
+    split's table; rows outside first .. first + B - 1 are not touched).  One launch on the current stream, nothing comes back to the host.
+    events: a pair of torch.cuda.Event recorded right before / after the launch (tools/threshold_sweep_time.py)."""
+    _expect("count_sweep", torch.float32, prob=prob, thresholds=thresholds)
+    _expect("count_sweep", torch.int32, table=table)
+    if prob.dim() != 2 or thresholds.dim() != 1 or table.dim() != 2 or table.shape[1] != thresholds.shape[0] or not table.is_contiguous() \
+            or not prob.is_contiguous() or not thresholds.is_contiguous():
+        raise RuntimeError(f"count_sweep: contiguous prob [B, Q], thresholds [T], table [N, T] expected, got {tuple(prob.shape)}, "
+                           f"{tuple(thresholds.shape)}, {tuple(table.shape)}")
+    if thresholds.device != prob.device or table.device != prob.device:
+        raise RuntimeError(f"count_sweep: prob on {prob.device}, thresholds on {thresholds.device}, table on {table.device}")
+    (B, Q), (N, T) = prob.shape, table.shape
+    with _between(events):
+        check(lib().cdetr_count_sweep(ptr(prob), ptr(thresholds), B, Q, T, ptr(table), N, int(first), stream_ptr()), "cdetr_count_sweep")
+
+
+class ThresholdSweep:
+    """The counts of a whole split at T thresholds on the device, filled batch by batch by cdetr_count_sweep (`emit`) and read back ONCE
+    (`finish`); shaped like DetectionStore.  `thresholds`: host numbers; each is rounded to fp32 once (numpy.float32), duplicates of the
+    rounded values are dropped and the rest sorted ascending -- `.thresholds` (float32 [T], T <= 32) names the table's columns."""
+
+    def __init__(self, n_images, thresholds, device):
+        import numpy as np
+        self.N = int(n_images)
+        self.thresholds = np.unique(np.asarray(list(thresholds), dtype=np.float64).astype(np.float32))
+        T = len(self.thresholds)
+        if self.N < 1 or not 1 <= T <= 32 or np.isnan(self.thresholds).any():
+            raise RuntimeError(f"ThresholdSweep: N = {self.N} images, {T} distinct thresholds (1 .. 32, no NaN)")
+        self.thr = torch.from_numpy(self.thresholds).to(device)
+        self.table = torch.zeros((self.N, T), dtype=torch.int32, device=device)
+        self.first, self._host = 0, None
+
+    def emit(self, prob, events=None):
+        """Append one forwarded batch (prob fp32 [B, Q]); nothing is awaited.  -> the table row of the batch's first image."""
+        first, B = self.first, prob.shape[0]
+        if first + B > self.N:
+            raise RuntimeError(f"ThresholdSweep: image {first + B} into a table of {self.N}")
+        count_sweep(prob, self.thr, self.table, first, events=events)
+        self.first, self._host = first + B, None
+        return first
+
+    def finish(self):
+        """ONE device -> host copy (it waits for the emits) -> counts int32 [n, T] of the n images emitted so far."""
+        if self._host is None:
+            self._host = self.table[:self.first].cpu().numpy()
+        return self._host
+
+
 class CriterionFn(torch.autograd.Function):
     """SetCriterion's six scalars in one launch (cdetr_criterion_fwd); returns (vec, total) with
     vec = [loss_ce, class_error, cardinality_error, loss_bbox, loss_giou, loss_variance] and total = sum_k w6[k] vec[k] (the weighted

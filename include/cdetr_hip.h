@@ -627,6 +627,17 @@ typedef struct {
 } cdetr_emit_detections_desc;
 int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream);
 
+/* ---- the counting rule at T thresholds in one pass (csrc/threshold_sweep.hip; infer.py --sweep_thresholds).
+ * cdetr_count_sweep: table[first + b][t] = #{q : prob[b][q] >= thresholds[t]} for the B images of a forwarded batch, fp32 compares (a NaN
+ *   probability is never counted), EQUAL to numpy's `prob >= numpy.float32(t)` summed over the row.  One launch, one workgroup per image:
+ *   every query's bin k = #{t : p >= thresholds[t]} goes through wave ballots and popcounts into an LDS histogram of T + 1 integer bins,
+ *   whose suffix sums are the row -- which is why `thresholds` must be ASCENDING (equal neighbours allowed).  Integer arithmetic only, no
+ *   atomic in global memory, one writer per cell: deterministic.  `table` is the device-resident [N][T] table of one split; only rows
+ *   first .. first + B - 1 are written.  Limits: any Q >= 1; 1 <= T <= 32 and B <= 65535, CDETR_ERR_UNSUPPORTED beyond; first >= 0 and
+ *   first + B <= N, CDETR_ERR_ARG otherwise (B, Q, T < 1 too).  Nothing is launched on an error.                                           */
+int cdetr_count_sweep(const float* prob, const float* thresholds, int32_t B, int32_t Q, int32_t T, int32_t* table, int32_t N, int32_t first,
+                      void* stream);
+
 /* ---- stage-1 pseudo labels emitted on the device (csrc/stage1_labels.hip): what the 1st stage's label writer does per annotated dot on the
  * host between the forward and pseudo_bbox_<split>.json (A1/engine.py:124-187; stage1.write_pseudo_labels' loop), plus the offline
  * evaluator's reading of that file (A1/offline_coco_evaluator.py:134-143: [cx, cy, w, h] -> a detection [cx - w/2, cy - h/2, w, h] of score

@@ -20,8 +20,18 @@ losses stay what they are at batch 1, per-image quantities averaged over the spl
 would get alone (one batched match + one cdetr_criterion_eval launch per batch), where the batched `forward` would normalise by the batch's
 target count.  The json lists the images in the order they were run; AP and the counting metrics do not depend on it.
 
+`--threshold T` (default 0.5) moves the counting rule's bar: `prob >= float32(T)` in fp32, a NaN never kept (threshold_sweep.py states the rule);
+`--threshold ckpt` takes the threshold main.py --calibrate_threshold left in the --resume checkpoint.  `--sweep_thresholds SPEC` (lo:hi:n or a
+comma list, at most 32 values, --threshold included) reports the counting metrics and the AP at every threshold from the SAME pass into
+threshold_sweep_<split>.json ({"thresholds", "rows", "best"}); everything else the run writes and prints stays what it is without the flag.  On
+the device path the store is emitted at the lowest threshold, one cdetr_count_sweep launch per batch counts every threshold, and ONE matching
+gives every threshold's AP (the detections kept at a higher threshold are a prefix of the evaluation order: coco_ap.accumulate_sweep); on
+the host path the same report comes from numpy and coco_ap.summarize_sweep, the slow checker.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --sweep_thresholds 0.3:0.7:9
+  python infer.py -dp /data/FSC147 --split test --resume out/detr_retrain.pth -o out --device_detections --threshold ckpt
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --eval_batch_size 16
 """
 import json
@@ -32,13 +42,14 @@ import torch
 import counting_detr_amd
 from counting_detr_amd import data
 from counting_detr_amd.args import get_args_parser
+from counting_detr_amd.coco_ap import gt_from_json, reference_box, summarize_sweep
 from counting_detr_amd.engine import count_from_logits, counting_metrics
 from counting_detr_amd.misc import NestedTensor
 
 
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True):
+          per_image=False, engine=None, write_json=True, sweep=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -48,7 +59,15 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     `engine`: an InferenceEngine of `model` made by the caller instead of a new one per call (main.py --eval_every: one engine riding on the
     trainer, engine.InferenceEngine(trainer=...), its captured forwards reused pass after pass; its weight images are brought up to date
     here, `engine.sync()`, before the first forward).  `write_json=False`: no predictions file is written or removed (the device path then
-    returns None for the predictions dict instead of building it); the metrics are the same either way."""
+    returns None for the predictions dict instead of building it); the metrics are the same either way.
+    `threshold`: rounded to fp32 once (threshold_sweep.widen), the rule everywhere below.  `sweep` (a threshold_sweep.Sweep whose thresholds
+    include `threshold`): the same pass also forms the counts of every image at every threshold of the sweep -- and, with `sweep.gt_json`, the
+    six AP numbers per threshold --, leaves them in `sweep.report` / `sweep.counts` and writes threshold_sweep_<split>.json; the returned
+    metrics and the predictions file are those of a pass without it."""
+    from counting_detr_amd import threshold_sweep as ts
+    threshold = ts.widen(threshold)
+    if sweep is not None:
+        ts.column(sweep.thresholds, threshold)              # raises unless the run's own threshold is one of the sweep's
     output_path = os.path.join(output_dir, "predictions_" + split + ".json") if write_json else None
     if output_path is not None and os.path.isfile(output_path):
         os.remove(output_path)
@@ -57,15 +76,18 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     if engine is None:
         from counting_detr_amd.engine import InferenceEngine
         engine = InferenceEngine(model, threshold, graphs=graphs and torch.device(device).type == "cuda", device=device)
-    elif engine.model is not model or engine.threshold != threshold:
+    elif engine.model is not model or ts.widen(engine.threshold) != threshold:
         raise ValueError("infer: the engine passed in was built for another model or threshold")
     elif getattr(engine, "trainer", None) is not None:
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
-        return _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image)
+        out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep)
+        _write_sweep(sweep, output_dir, split)
+        return out
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
     pred_counts, gt_counts, loss_sum, n_img = [], [], {}, 0
+    tables, dt_by, image_ids = [], {}, []           # sweep: count rows per batch, the detections kept at the sweep's lowest threshold
     def lookahead(loader):          # (batch on the device, the next batch's image tensor or None): the engine runs the next image's frozen
         prev = None                 # stage (stem + layer1) beside this image's encoder / decoder
         for cur in loader:
@@ -94,6 +116,11 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
             ori_h, ori_w = [int(x) for x in ret["orig_size"][b]]
             image_id = int(ret["image_id"][b]) if "image_id" in ret else n_img
             kb = keep[b]
+            if sweep is not None:                   # everything the lowest threshold keeps; the file takes those at `threshold`
+                if b == 0:
+                    prob_h = prob.cpu().numpy()
+                    tables.append(ts.count_table(prob_h, sweep.thresholds))
+                kb = torch.from_numpy(ts.kept(prob_h[b], sweep.thresholds[0])).to(prob.device)
             scores = prob[b][kb].cpu().numpy()
             boxes = outputs["pred_boxes"][b][kb].cpu().numpy().copy()
             pts = ref_points[b][kb].cpu().numpy().copy()
@@ -101,13 +128,19 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
             boxes[..., 0] *= ori_w; boxes[..., 1] *= ori_h; boxes[..., 2] *= ori_w; boxes[..., 3] *= ori_h
             for sc, bx, pt in zip(scores, boxes, pts):
                 x_cen, y_cen, w, h = bx
+                if sweep is not None:
+                    box = reference_box([int(x_cen), int(y_cen), int(w), int(h)])
+                    dt_by.setdefault(image_id, []).append({"bbox": box, "score": float(sc), "area": float(box[2] * box[3])})
+                    if not ts.kept(sc, threshold):
+                        continue
                 predictions["annotations"].append({"id": anno_id, "image_id": image_id, "area": int(w * h),
                                                    "bbox": [int(x_cen), int(y_cen), int(w), int(h)], "category_id": 1,
                                                    "score": float(sc), "point": [int(pt[0]), int(pt[1])]})
                 anno_id += 1
             predictions["images"].append({"id": image_id, "height": ori_h, "width": ori_w, "file_name": "None"})
-            pred_counts.append(int(kb.sum()))
+            pred_counts.append(int(kb.sum()) if sweep is None else int(tables[-1][b, ts.column(sweep.thresholds, threshold)]))
             gt_counts.append(int(targets[b]["boxes"].shape[0]))
+            image_ids.append(image_id)
             n_img += 1
     if output_path is not None:
         with open(output_path, "w") as handle:
@@ -116,7 +149,22 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     if n_img:       # images without objects contribute to MAE / RMSE only (the reference divides by the count, A2/eval_all.py:264-265)
         metrics.update(counting_metrics(pred_counts, gt_counts))
     metrics["images"] = n_img
+    if sweep is not None and n_img:
+        import numpy as np
+        ap_rows = None
+        if sweep.gt_json is not None:
+            ap_rows = summarize_sweep(gt_from_json(sweep.gt_json, image_ids), dt_by, sweep.thresholds)
+        sweep.counts = np.concatenate(tables)
+        sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows)
+    _write_sweep(sweep, output_dir, split)
     return metrics, predictions
+
+
+def _write_sweep(sweep, output_dir, split):
+    """threshold_sweep_<split>.json of a pass that swept (nothing otherwise)."""
+    if sweep is not None and sweep.report is not None:
+        with open(os.path.join(output_dir, "threshold_sweep_" + split + ".json"), "w") as handle:
+            json.dump(sweep.report, handle)
 
 
 def _num_images(data_loader):
@@ -129,20 +177,25 @@ def _num_images(data_loader):
     raise RuntimeError("infer: device_detections needs the number of images up front (a DataLoader, a data.Prefetcher or a list of batches)")
 
 
-def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False):
+def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
     and image ids into a device table.  After the loop: one copy each of the store, the table and the loss buffer; the json is written from the
     store's arrays (same bytes as the host loop's file), the losses are summed in Python in the same order (same floats), the counts are the
-    store's, and the AP (`gt_json`) is coco_ap.summarize_store on the store -- the file is not read back."""
+    store's, and the AP (`gt_json`) is coco_ap.summarize_store on the store -- the file is not read back.
+    `sweep`: the store is emitted at the sweep's LOWEST threshold and one cdetr_count_sweep call per batch (ops.ThresholdSweep) sits beside the
+    emit; after the loop one more copy brings the [N, T] table.  The file takes the wire records with score >= `threshold` (query order, ids
+    from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, and the AP of every threshold comes
+    from ONE matching (coco_ap.summarize_store_sweep), the returned six numbers being its row at `threshold`."""
     import numpy as np
     from counting_detr_amd import ops
-    from counting_detr_amd.coco_ap import MAX_DETS, gt_from_json, summarize_store
+    from counting_detr_amd import threshold_sweep as ts
+    from counting_detr_amd.coco_ap import MAX_DETS, summarize_store, summarize_store_sweep
     if device.type != "cuda":
         raise RuntimeError(f"infer: device_detections runs HIP kernels, device={device} has none (the default is the host path)")
     N = _num_images(data_loader)
-    store = meta = loss_buf = loss_keys = None
+    store = meta = loss_buf = loss_keys = table = None
     n_targets, gt_counts, n_img, n_batch = [], [], 0, 0
     with torch.cuda.device(device):
         for ret in data_loader:
@@ -153,7 +206,8 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             loss_dict = criterion.per_image(outputs, targets) if per_image else criterion(outputs, targets)
             B, Q = prob.shape
             if store is None:
-                store = ops.DetectionStore(N, Q, device, threshold=threshold, max_det=MAX_DETS)
+                store = ops.DetectionStore(N, Q, device, threshold=threshold if sweep is None else sweep.thresholds[0], max_det=MAX_DETS)
+                table = ops.ThresholdSweep(N, sweep.thresholds, device) if sweep is not None else None
                 meta = torch.zeros((N, 3), dtype=torch.int64, device=device)                # ori_h, ori_w, image id
                 loss_keys = list(loss_dict)
                 loss_buf = torch.zeros((N, len(loss_keys)), dtype=torch.float64, device=device)      # fp32 -> fp64 is exact: float(v) of the host loop
@@ -174,6 +228,8 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             else:
                 rows[:, 2].copy_(torch.arange(n_img, n_img + B))
             store.emit(prob.contiguous(), outputs["pred_boxes"].contiguous(), ref_points.reshape(B, Q, 2).contiguous(), rows[:, :2].to(torch.int32))
+            if table is not None:
+                table.emit(prob.contiguous())
             gt_counts += [int(t["boxes"].shape[0]) for t in targets]
             n_img += B
         predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
@@ -186,10 +242,17 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
                     loss_sum[k] = loss_sum.get(k, 0.0) + v * n_t
             pred_counts = host["counts"].tolist()
             image_ids = [m[2] for m in meta_h]
+            wire_np, score_np, per_image = host["wire"], host["score"], np.diff(host["wire_off"]).tolist()
+            if sweep is not None:                   # the store holds what the lowest threshold keeps: the file and the counts are `threshold`'s
+                col = ts.column(sweep.thresholds, threshold)
+                sweep.counts = table.finish()
+                pred_counts = sweep.counts[:, col].tolist()
+                at_thr = ts.kept(score_np, threshold)
+                owner = np.repeat(np.arange(n_img), per_image)
+                wire_np, score_np, per_image = wire_np[at_thr], score_np[at_thr], np.bincount(owner[at_thr], minlength=n_img).tolist()
         if n_img and output_path is not None:
-            per_image = np.diff(host["wire_off"]).tolist()
             ann_image = [i for i, c in zip(image_ids, per_image) for _ in range(c)]
-            wire, score = host["wire"].tolist(), host["score"].astype(np.float64).tolist()
+            wire, score = wire_np.tolist(), score_np.astype(np.float64).tolist()
             predictions["annotations"] = [{"id": k + 1, "image_id": i, "area": w[4], "bbox": w[:4], "category_id": 1, "score": sc, "point": w[5:7]}
                                           for k, (i, w, sc) in enumerate(zip(ann_image, wire, score))]
             predictions["images"] = [{"id": m[2], "height": m[0], "width": m[1], "file_name": "None"} for m in meta_h]
@@ -202,7 +265,14 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
         if n_img:
             metrics.update(counting_metrics(pred_counts, gt_counts))
         metrics["images"] = n_img
-        if gt_json is not None and n_img:
+        if sweep is not None and n_img:
+            ap_json, ap_rows = sweep.gt_json if sweep.gt_json is not None else gt_json, None
+            if ap_json is not None:
+                ap_rows = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds)
+                if gt_json is not None:
+                    metrics.update(ap_rows[col])
+            sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
+        elif gt_json is not None and n_img:
             metrics.update(summarize_store(gt_from_json(gt_json, image_ids), store, image_ids))
     return metrics, predictions
 
@@ -240,16 +310,39 @@ def eval_loader(args, device):
     return dl, B > 1
 
 
-def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, write_json=True):
+def run_threshold(args):
+    """--threshold as the number the pass uses (fp32, widened); `ckpt` has been replaced by the checkpoint's value before (`main`)."""
+    from counting_detr_amd.threshold_sweep import widen
+    t = getattr(args, "threshold", 0.5)
+    if t == "ckpt":
+        raise ValueError("--threshold ckpt: only infer.py reads the threshold from the --resume checkpoint")
+    return widen(t)
+
+
+def build_sweep(args):
+    """--sweep_thresholds -> a threshold_sweep.Sweep for one pass (--threshold merged in; AP columns when instances_<split>.json is there), or None."""
+    if not getattr(args, "sweep_thresholds", None):
+        return None
+    from counting_detr_amd.threshold_sweep import Sweep, parse_spec
+    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+    return Sweep(parse_spec(args.sweep_thresholds, run_threshold(args)), gt_json if os.path.isfile(gt_json) else None)
+
+
+def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, write_json=True, sweep=None):
     """One pass over `dl` (eval_loader) -> the metrics this file prints: mean losses, MAE / RMSE / NAE / SRE, `images`, and the six AP numbers
     when the split's instances json is there.  `engine` / `write_json`: see `infer` (main.py --eval_every passes its riding engine); the
-    file is written regardless when the AP has to be read back from it (no --device_detections, or --ap_on_host)."""
+    file is written regardless when the AP has to be read back from it (no --device_detections, or --ap_on_host).  --threshold and
+    --sweep_thresholds act here; `sweep`: the caller's own `build_sweep(args)`, whose report it reads after the pass."""
     gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
     on_device = bool(getattr(args, "device_detections", False))
     ap_in_loop = on_device and os.path.isfile(gt_json) and not getattr(args, "ap_on_host", False)      # matched from the device-resident detections
     ap_from_file = os.path.isfile(gt_json) and not ap_in_loop
-    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
-                       gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file)
+    threshold = run_threshold(args)
+    if sweep is None:
+        sweep = build_sweep(args)
+    metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
+                       gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
+                       sweep=sweep)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
@@ -265,6 +358,11 @@ def main(args):
     if args.resume:
         ckpt = torch.load(args.resume, map_location="cpu", weights_only=False)
         model.load_state_dict(ckpt["model"], strict=True)
+    if getattr(args, "threshold", 0.5) == "ckpt":                       # the threshold main.py --calibrate_threshold left in the checkpoint
+        from counting_detr_amd.threshold_sweep import checkpoint_threshold
+        if not args.resume:
+            raise ValueError("--threshold ckpt needs --resume: the threshold is read from that checkpoint")
+        args.threshold = checkpoint_threshold(ckpt, args.resume)
     dl, per_image = eval_loader(args, device)
     os.makedirs(args.output_dir, exist_ok=True)
     metrics = evaluate_split(model, criterion, dl, per_image, device, args)

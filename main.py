@@ -11,6 +11,9 @@ and the resize / normalisation / padding of a batch is one launch on the prefetc
 --eval_every N: the validation call the reference left commented out (A2/main.py "Evaluate ...").  After every N-th epoch and the last one rank 0
 walks --split through infer.py's loop on the live weights (an InferenceEngine riding on the trainer: no graph is dropped on either side), the
 epoch's log line gains test_<k>, and --keep_best {mae,ap,loss} also saves the best epoch to detr_retrain_best.pth ("best" in every checkpoint).
+--threshold T / --sweep_thresholds SPEC reach that pass and --eval (infer.py); with --calibrate_threshold {mae,rmse,nae,sre,ap} the sweep's best
+threshold follows the test_* keys as test_best_threshold / test_best_<metric> (the test_* keys themselves stay at --threshold) and every checkpoint
+written from then on carries "count_threshold": {"metric", "threshold", "value", "epoch"}, which `infer.py --threshold ckpt` reads.
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --synthetic --no_aux_loss ...
@@ -63,12 +66,14 @@ class Validator:
         from counting_detr_amd.engine import InferenceEngine
         self._infer, self.trainer, self.criterion, self.args, self.device = _infer, trainer, criterion, args, device
         self.loader, self.per_image = _infer.eval_loader(args, device)
-        self.engine = InferenceEngine(trainer.model, graphs=device.type == "cuda", device=device, trainer=trainer)
+        self.engine = InferenceEngine(trainer.model, _infer.run_threshold(args), graphs=device.type == "cuda", device=device, trainer=trainer)
+        self.sweep = None                                               # --sweep_thresholds: the last pass's threshold_sweep.Sweep (its report)
 
     def run(self, write_json=True):
         try:
+            self.sweep = self._infer.build_sweep(self.args)
             return self._infer.evaluate_split(self.trainer.model, self.criterion, self.loader, self.per_image, self.device, self.args,
-                                              engine=self.engine, write_json=write_json)
+                                              engine=self.engine, write_json=write_json, sweep=self.sweep)
         finally:
             self.trainer.model.train()
             self.criterion.train()
@@ -109,10 +114,17 @@ def main(args):
             print(f"resume: optimizer state restored, continuing at epoch {resumed} (checkpoint epoch {resumed - 1})")
             args.start_epoch = resumed
     # --eval_every: validation inside the run, on the trainer's own weight images (engine.InferenceEngine(trainer=...)), + the best checkpoint
-    keeper = validator = last_metrics = None
+    keeper = validator = last_metrics = count_threshold = None
+    calibrate = getattr(args, "calibrate_threshold", None)
+    if calibrate and not (args.eval_every > 0 and getattr(args, "sweep_thresholds", None)):
+        raise SystemExit("--calibrate_threshold picks from a validation pass's sweep: it needs --eval_every N and --sweep_thresholds SPEC")
     if args.eval_every > 0:
         if args.synthetic:
             raise SystemExit("--eval_every validates on a dataset split: not with --synthetic")
+        if calibrate == "ap" and not os.path.isfile(os.path.join(args.data_path, "instances_" + args.split + ".json")):
+            raise SystemExit("--calibrate_threshold ap needs the split's box ground truth (instances_<split>.json): it is not there")
+        if checkpoint is not None and (args.resume_optimizer or args.auto_resume):
+            count_threshold = checkpoint.get("count_threshold")          # a resumed run keeps the calibration until its next calibrated pass
         keeper = ckpt_io.BestKeeper(args.keep_best, os.path.isfile(os.path.join(args.data_path, "instances_" + args.split + ".json")))
         if checkpoint is not None and (args.resume_optimizer or args.auto_resume):
             keeper.load(checkpoint.get("best"))           # a resumed run never overwrites a better detr_retrain_best.pth with a worse one
@@ -151,6 +163,12 @@ def main(args):
                 test_stats = {"loss": ckpt_io.weighted_loss(last_metrics, criterion.weight_dict), **last_metrics}
                 if keeper.update(test_stats, epoch):
                     paths.append(output_dir / "detr_retrain_best.pth")
+                if calibrate:   # the sweep's best threshold of this pass: behind the test_* keys, and into the checkpoints from here on
+                    from counting_detr_amd.threshold_sweep import calibration
+                    found = calibration(validator.sweep.report, calibrate, epoch) if validator.sweep.report else None
+                    if found is not None:
+                        count_threshold = found
+                        test_stats["best_threshold"], test_stats["best_" + calibrate] = found["threshold"], found["value"]
             if utils.is_dist_avail_and_initialized():
                 torch.distributed.barrier()
         if utils.is_main_process():            # only rank 0 pays for the host copy of the moments
@@ -158,6 +176,8 @@ def main(args):
                     "epoch": epoch, "args": args}
             if keeper is not None:
                 ckpt["best"] = keeper.state()
+            if count_threshold is not None:
+                ckpt["count_threshold"] = dict(count_threshold)
             for p in paths:
                 torch.save(ckpt, p)
         if utils.is_main_process():
@@ -172,8 +192,9 @@ def main(args):
             dl, per_image = _infer.eval_loader(args, device)           # --eval_batch_size: batches of one resized size, per-image losses
             on_device = bool(getattr(args, "device_detections", False))      # post-forward work + box AP on the device (infer.py)
             gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
-            metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, device_detections=on_device,
-                                      gt_json=gt_json if on_device and os.path.isfile(gt_json) else None, per_image=per_image)
+            metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=_infer.run_threshold(args),
+                                      device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
+                                      per_image=per_image, sweep=_infer.build_sweep(args))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
