@@ -360,6 +360,14 @@ __device__ __forceinline__ void nat_stash(const NatRegs& r, __bf16* tile, int ti
         stash_split4(tile + (idx >> 3) * TS + (idx & 7) * 4, 32, r.v[s].x, r.v[s].y, r.v[s].z, r.v[s].w);
     }
 }
+// the same with every element multiplied by `mul` before the split (own_frag's `scale` for a staged tile)
+__device__ __forceinline__ void nat_stash(const NatRegs& r, __bf16* tile, int tid, float mul) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int idx = tid + NTF * s;
+        stash_split4(tile + (idx >> 3) * TS + (idx & 7) * 4, 32, r.v[s].x * mul, r.v[s].y * mul, r.v[s].z * mul, r.v[s].w * mul);
+    }
+}
 // transposed tile (64 threads `t`): block (row quad kq = t & 7, column quad cq = t >> 3) = 4 rows x 4 columns
 __device__ __forceinline__ void tr_fetch(TrRegs& r, const float* __restrict__ src, long ld, int col0, int r0, int L, int t) {
 #pragma unroll
@@ -695,7 +703,11 @@ __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], c
     const float* on = o + (long)n * Sq * E;
     const float* lsn = lse + ((long)n * nh + head) * Sq;
     bf16x8 kh[2], kl[2], vh[2], vl[2];
-    own_frag(kg + ((long)n * Sk + jc) * ldk + head * D, g, scale, kh, kl);
+    // The scale goes on the QUERY side, before the split, as in the forward and in bwd_q_body: S^T is then the sum of the same three bf16
+    // products per element as the S behind `lse` (split(q * scale) x split(k)), and the split's truncation -- ~2^-17 of sum |q_c k_c|, 1e-4
+    // at the logit magnitudes of peaked or offset rows -- cancels in p = exp(S - lse).  With it on the key side (split(q) x split(k * scale))
+    // the two truncations were independent: every p, and with it dV and dK, carried that 1e-4 as a relative error (dQ did not).
+    own_frag(kg + ((long)n * Sk + jc) * ldk + head * D, g, 1.f, kh, kl);
     own_frag(vg + ((long)n * Sk + jc) * ldv + head * D, g, 1.f, vh, vl);
     f32x16 dKT = zero16(), dVT = zero16();
     constexpr int PD = 3;
@@ -715,7 +727,7 @@ __device__ __forceinline__ void bwd_kv_body(__bf16* lds, float (*stat)[2][32], c
     };
     auto stash = [&](const Ring& r, int buf) __attribute__((always_inline)) {
         __bf16* nb = lds + buf * 4 * TILE;
-        nat_stash(r.q, nb, tid);
+        nat_stash(r.q, nb, tid, scale);                                          // Q * scale for S^T; Q^T below stays unscaled (dK is scaled once, at the store)
         nat_stash(r.d, nb + TILE, tid);
         tr_stash(r.t, nb + (wid == 0 ? 2 : 3) * TILE, lane);
         if (tid < 32) stat[buf][0][tid] = r.s;

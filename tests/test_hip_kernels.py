@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attn_edges_ref import rcda_core_ref      # the fp64 RCDA closed form, shared with the edge-case tests
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -193,23 +195,6 @@ def test_maxpool():
 
 
 # ----------------------------------------------------------------------------------------------------- RCDA core
-def rcda_core_ref(qr, qc, kr, kc, v, mr, mc, nh):
-    """fp64 restatement of A2/models/row_column_decoupled_attention.py:215-309 on projected inputs."""
-    N, L, E = qr.shape
-    H, W = v.shape[1:3]
-    d = E // nh
-    hs = lambda t: t.reshape(N, -1, nh, d).permute(0, 2, 1, 3)   # noqa: E731
-    s_row = (hs(qr) * d ** -0.5) @ hs(kr).transpose(-1, -2)
-    s_col = (hs(qc) * d ** -0.5) @ hs(kc).transpose(-1, -2)
-    if mr is not None:
-        s_row = s_row.masked_fill(mr.bool()[:, None, None, :], float("-inf"))
-        s_col = s_col.masked_fill(mc.bool()[:, None, None, :], float("-inf"))
-    a_row, a_col = s_row.softmax(-1), s_col.softmax(-1)
-    vv = v.reshape(N, H, W, nh, d).permute(0, 3, 1, 2, 4)
-    o = torch.einsum("bnqh,bnqw,bnhwc->bnqc", a_col, a_row, vv)
-    return o.permute(0, 2, 1, 3).reshape(N, L, E)
-
-
 @pytest.mark.parametrize("N,L,H,W,masked", [(2, 300, 50, 50, False), (1, 600, 20, 30, True), (2, 77, 7, 5, True),
                                             (1, 130, 70, 40, True), (2, 2500, 50, 50, True), (1, 33, 24, 36, False),
                                             (1, 200, 40, 84, True), (1, 100, 84, 70, False), (1, 64, 16, 64, True),   # W > 64: the wide-map kernels
