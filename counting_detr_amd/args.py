@@ -119,6 +119,12 @@ def get_args_parser():
     p.add_argument("--calibrate_threshold", default=argparse.SUPPRESS, choices=["mae", "rmse", "nae", "sre", "ap"],
                    help="main.py with --eval_every and --sweep_thresholds: the sweep's best threshold for this metric goes into the epoch's log "
                         "line (test_best_threshold, test_best_<metric>) and into every checkpoint written afterwards (count_threshold)")
+    # like the three above: no attribute when it is not given
+    p.add_argument("--image_report", action="store_true", default=argparse.SUPPRESS,
+                   help="infer.py / main.py --eval / --eval_every: also say on WHICH images the model fails -- image_report_<split>.json beside the "
+                        "predictions file (per image: counts, diff, its own AP numbers, tp / fp / fn at IoU 0.5; the images ordered by AP and by "
+                        "diff) and six average-recall keys (AR900, AR1000, AR1100, ARs, ARm, ARl) in the metrics.  Needs instances_<split>.json.  "
+                        "With --device_detections: one cdetr_coco_image_stats launch on the flags of the split's one matching")
     return p
 
 

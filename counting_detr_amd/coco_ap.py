@@ -35,6 +35,15 @@ SCORE-THRESHOLD SWEEP (`summarize_store_sweep`, infer.py --sweep_thresholds): th
 the lowest of them -- in evaluation order the detections a higher threshold keeps are a prefix, per image and after the merge, and a greedy
 match never looks ahead (`accumulate_sweep`).  `summarize_sweep` filters and evaluates once per threshold on the host: slow,
 and the checker (tests/test_threshold_sweep_cpu.py, _gpu.py).
+
+PER-IMAGE STATISTICS (`image_stats`, `image_stats_store`, infer.py --image_report): the list the reference's evaluator keeps per image
+(A2/eval_all.py:227-239, its `ap` field left empty at line 181) and the counts behind COCOevalMaxDets.summarize's stats[6..11], AR at maxDets
+900 / 1000 / 1100 and AR small / medium / large, which the six numbers above do not restate.  Both come from the flags of the ONE matching: the
+first `c` detections of an image are an evaluation at max_det = c (COCOeval matches once and slices afterwards), and an image's own AP is
+`_sample` on its own list.  `stats_from_flags` states that in numpy and is the checker; on the device ONE cdetr_coco_image_stats launch
+(csrc/coco_report.hip) reads the flags where cdetr_coco_match left them and returns EQUAL numbers, the average precisions bit for bit
+(tests/test_image_report_cpu.py, _gpu.py).  `average_recall`, `image_rows` and `image_report` turn the statistics into what is
+printed and written.
 """
 import json
 
@@ -164,7 +173,7 @@ def _merged_cumulative(scores, matched, ignored):
 def _sample(tps, fps, npig):
     """The tail of `accumulate`, shared with `accumulate_sweep`: cumulative tp / fp [T, N] of a merged list and its npig > 0 -> precision
     [T, R]: recall and precision, the envelope from the right, the 101-point sampling (zeros for an empty list)."""
-    T, R = len(IOU_THRS), len(REC_THRS)
+    T, R = tps.shape[0], len(REC_THRS)
     precision = np.zeros((T, R))
     N = tps.shape[1]
     if N == 0:
@@ -186,11 +195,13 @@ def _cuda(device):
     return device
 
 
-def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None):
+def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None, keep=None, host=True):
     """One `cdetr_coco_match` launch for every image of `pack` (from `pack_images`) under the area ranges `areas` ->
     (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int): `_evaluate_image`'s flags, images side by side.
     `events`: a pair of torch.cuda.Event recorded around the launch.  A pack that carries "dt_device" = (boxes f64 [D, 4], area f64 [D]) device
-    tensors (`summarize_store`) has its detections read from there; its dt_boxes / dt_area are not used."""
+    tensors (`summarize_store`) has its detections read from there; its dt_boxes / dt_area are not used.
+    `keep`: a list that also receives the three device tensors the launch wrote (`_stats_on_device` reads them where they are);
+    `host=False`: only those, no copy (B > 0)."""
     import torch
     from . import ops
     device = _cuda(device)
@@ -212,8 +223,13 @@ def match_on_device(pack, device, areas=("all", "small", "medium", "large"), eve
         gt_boxes, gt_area, dt_boxes, dt_area, d_thrs, d_rng = (f[cuts[k]:cuts[k + 1]] for k in range(6))
         if dt_dev is not None:
             dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
+        if not host:
+            on_dev = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]), events=events)
+            if keep is not None:
+                keep.extend(on_dev)
+            return on_dev
         matched, ignored, npig = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]),
-                                                host=True, events=events)
+                                                host=True, events=events, keep=keep)
     return matched, ignored, npig
 
 
@@ -316,19 +332,38 @@ def pack_store(gt_by_img, store, image_ids):
             "dt_score": np.ascontiguousarray(score), "dt_off": np.concatenate([[0], np.cumsum([n_dt(i) for i in ids])]).astype(np.int32)}
 
 
-def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS):
-    """`summarize(..., device=)` for an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections): the same six numbers
-    as `ap_from_json(device=)` gives on the predictions json written from that store, without the json trip -- the evaluation records go to
-    cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image k; `gt_by_img` as for `summarize`
-    (`gt_from_json`).  `device`: the store's own (default)."""
+def _store_flags(gt_by_img, store, image_ids, device, max_det, report):
+    """The shared head of `summarize_store` / `summarize_store_sweep`: the store's pack and the flags of its ONE cdetr_coco_match launch on the
+    host -> (pack, matched, ignored, npig, stats); `report` = (cuts, counts) also runs cdetr_coco_image_stats on the flags where the launch
+    left them (`stats`: the dict of `image_stats`, else None).  counts[k] belongs to the store's image k."""
     if store.max_det != max_det:
         raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
     device = store.buf.device if device is None else _cuda(device)
     pack = pack_store(gt_by_img, store, image_ids)
-    areas = tuple(AREA_RNG)
-    matched, ignored, npig = match_on_device(pack, device, areas)
-    by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(areas)}
-    return _six(by_area)
+    keep = [] if report is not None else None
+    matched, ignored, npig = match_on_device(pack, device, tuple(AREA_RNG), keep=keep)
+    stats = None
+    if report is not None:
+        cuts, counts = report
+        if counts is not None:
+            slot = {int(i): k for k, i in enumerate(image_ids)}
+            counts = [int(counts[slot[i]]) if i in slot else 0 for i in pack["image_ids"]]
+        if keep:
+            stats = _stats_on_device(pack, keep, cuts, counts, npig, device)
+        else:                                                              # no image at all: nothing was launched
+            stats = _stats_dict([], *stats_from_flags(matched, ignored, [0], npig, cuts), npig, cuts)
+    return pack, matched, ignored, npig, stats
+
+
+def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS, report=None):
+    """`summarize(..., device=)` for an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections): the same six numbers
+    as `ap_from_json(device=)` gives on the predictions json written from that store, without the json trip -- the evaluation records go to
+    cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image k; `gt_by_img` as for `summarize`
+    (`gt_from_json`).  `device`: the store's own (default).
+    `report` = (cuts, counts): -> (the six numbers, the per-image statistics of `image_stats_store`) from the SAME matching launch."""
+    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report)
+    by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}
+    return _six(by_area) if report is None else (_six(by_area), stats)
 
 
 def accumulate_sweep(scores, matched, ignored, npig, thresholds):
@@ -368,21 +403,157 @@ def summarize_flags_sweep(scores, flags, thresholds):
     return [_six({a: per_area[a][k] for a in per_area}) for k in range(len(thresholds))]
 
 
-def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS):
+def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS, report=None):
     """`summarize_store` at every score threshold of `thresholds` from ONE cdetr_coco_match launch: the store was emitted at the lowest
     threshold (checked), the flags of every higher one are a prefix of what that launch returns (`accumulate_sweep`).  -> list of the six
-    numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold."""
+    numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold.
+    `report` = (cuts, counts): -> (that list, the per-image statistics of `image_stats_store`) from the same launch; counts[k] = the
+    detections of the store's image k that the threshold to be reported keeps (a prefix, as above)."""
     t32 = np.asarray(list(thresholds), dtype=np.float64).astype(np.float32)
     if len(t32) == 0 or np.isnan(t32).any() or np.float32(store.threshold) != t32.min():
         raise RuntimeError(f"coco_ap: a sweep over {t32.tolist()} needs a store emitted at its lowest threshold, this one was emitted at "
                            f"{store.threshold}")
-    if store.max_det != max_det:
-        raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
-    device = store.buf.device if device is None else _cuda(device)
-    pack = pack_store(gt_by_img, store, image_ids)
-    areas = tuple(AREA_RNG)
-    matched, ignored, npig = match_on_device(pack, device, areas)
-    return summarize_flags_sweep(pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(areas)}, t32)
+    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report)
+    rows = summarize_flags_sweep(pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}, t32)
+    return rows if report is None else (rows, stats)
+
+
+# ------------------------------------------------------------------------------------------------- per-image statistics and average recall
+MAX_DET_CUTS = (900, 1000, 1100)        # A2/eval_all.py:511-512: COCOeval's maxDets; its AR numbers are read at each, its AP at the last
+
+
+def stats_from_flags(matched, ignored, dt_off, npig, cuts, counts=None):
+    """The definition of cdetr_coco_image_stats in numpy (host only: the checker).  matched / ignored [A, T, D] of ONE matching (images side by
+    side, image b owns dt_off[b]:dt_off[b + 1], evaluation order), npig [A, B], `cuts` = maxDets cuts, `counts` [B] = use only the first
+    min(counts[b], segment) detections of image b.  -> tp, fp int32 [A, B, T, M]: true / false positives among the first min(cut, n) detections
+    of the image -- COCOeval matches once over dt[:maxDets[-1]] and slices [:, :maxDet] afterwards, so these are the counts of an evaluation at
+    max_det = cut --; ap float64 [A, B, T]: the image's OWN average precision (`_sample` on its own list, the R samples summed in index order),
+    -1 where the image has no non-ignored ground truth."""
+    matched, ignored = np.asarray(matched, dtype=bool), np.asarray(ignored, dtype=bool)
+    A, T, _ = matched.shape
+    dt_off = np.asarray(dt_off, dtype=np.int64)
+    B, M, R = len(dt_off) - 1, len(cuts), len(REC_THRS)
+    npig = np.asarray(npig).reshape(A, B)
+    tp, fp, ap = np.zeros((A, B, T, M), dtype=np.int32), np.zeros((A, B, T, M), dtype=np.int32), -np.ones((A, B, T))
+    for b in range(B):
+        lo, n = int(dt_off[b]), int(dt_off[b + 1] - dt_off[b])
+        if counts is not None:
+            n = min(n, max(int(counts[b]), 0))
+        for a in range(A):
+            m, ig = matched[a, :, lo:lo + n], ignored[a, :, lo:lo + n]
+            tps, fps = np.cumsum(m & ~ig, axis=1, dtype=np.float64), np.cumsum(~m & ~ig, axis=1, dtype=np.float64)
+            for k, c in enumerate(cuts):
+                c = min(max(int(c), 0), n)
+                if c:
+                    tp[a, b, :, k], fp[a, b, :, k] = tps[:, c - 1], fps[:, c - 1]
+            if npig[a, b] > 0:
+                ap[a, b] = np.cumsum(_sample(tps, fps, int(npig[a, b])), axis=-1)[..., -1] / R
+    return tp, fp, ap
+
+
+def _stats_dict(ids, tp, fp, ap, npig, cuts):
+    return {"image_ids": list(ids), "tp": tp, "fp": fp, "ap": ap, "npig": np.asarray(npig, dtype=np.int64), "cuts": tuple(int(c) for c in cuts)}
+
+
+def _stats_on_device(pack, flags, cuts, counts, npig, device):
+    """cdetr_coco_image_stats on the device tensors `flags` = (matched, det_ignored, npig) of `match_on_device(keep=)`: one launch, one copy
+    back.  `counts`: per image of the pack, or None; `npig`: the host copy the caller already holds."""
+    import torch
+    from . import ops
+    B, M = len(pack["image_ids"]), len(cuts)
+    i32 = np.concatenate([pack["dt_off"], np.asarray(cuts, dtype=np.int64), np.asarray([] if counts is None else counts, dtype=np.int64)])
+    with torch.cuda.device(device):
+        i = torch.from_numpy(i32.astype(np.int32)).to(device)
+        rec = torch.from_numpy(REC_THRS).to(device)
+        tp, fp, ap = ops.coco_image_stats(flags[0], flags[1], i[:B + 1], flags[2], i[B + 1:B + 1 + M], rec,
+                                          dt_cnt=None if counts is None else i[B + 1 + M:], host=True)
+    return _stats_dict(pack["image_ids"], tp, fp, ap, npig, cuts)
+
+
+def image_stats(gt_by_img, dt_by_img, cuts=MAX_DET_CUTS, device=None, max_det=MAX_DETS):
+    """Per-image statistics of one evaluation -> {"image_ids" (sorted, images with neither ground truth nor detection left out), "tp", "fp"
+    int32 [A, B, T, M], "ap" float64 [A, B, T] (-1: no non-ignored ground truth), "npig" [A, B], "cuts"}; A = the four area ranges of AREA_RNG
+    in its order, T = IOU_THRS, M = `cuts`.  device=None: `_evaluate_image`'s flags and `stats_from_flags`, the host path and the checker.  A
+    CUDA device: `pack_images`, ONE cdetr_coco_match launch, ONE cdetr_coco_image_stats launch on its flags where they lie, one copy of the
+    statistics back (and the 4 B ints of npig) -- EQUAL numbers, `ap` bit for bit."""
+    areas, T = tuple(AREA_RNG), len(IOU_THRS)
+    if device is not None:
+        device = _cuda(device)
+        pack = pack_images(gt_by_img, dt_by_img, max_det)
+        if pack["image_ids"]:
+            flags = match_on_device(pack, device, areas, host=False)
+            return _stats_on_device(pack, flags, cuts, None, flags[2].cpu().numpy(), device)
+    ids = [i for i in sorted(set(gt_by_img) | set(dt_by_img)) if gt_by_img.get(i) or dt_by_img.get(i)]
+    per = [[_evaluate_image(dt_by_img.get(i, []), gt_by_img.get(i, []), AREA_RNG[a], max_det) for i in ids] for a in areas]
+    cat = lambda k: np.stack([np.concatenate([e[k].reshape(T, -1) for e in row] + [np.zeros((T, 0), dtype=bool)], axis=1) for row in per])   # noqa: E731
+    dt_off = np.concatenate([[0], np.cumsum([len(e[0]) for e in per[0]])]).astype(np.int64)
+    npig = np.array([[e[3] for e in row] for row in per], dtype=np.int64).reshape(len(areas), len(ids))
+    return _stats_dict(ids, *stats_from_flags(cat(1), cat(2), dt_off, npig, cuts), npig, cuts)
+
+
+def image_stats_store(gt_by_img, store, image_ids, cuts=MAX_DET_CUTS, counts=None):
+    """`image_stats(device=)` for an ops.DetectionStore: the detections are read where cdetr_emit_detections left them.  `image_ids[k]` = the id
+    of the store's image k, `counts[k]` = use only its first counts[k] detections (a threshold above the store's own keeps a prefix).
+    `summarize_store(report=(cuts, counts))` gives the six AP numbers from the same matching launch."""
+    return summarize_store(gt_by_img, store, image_ids, report=(cuts, counts))[1]
+
+
+def average_recall(stats):
+    """The second half of COCOeval.summarize, stats[6..11] -> {"AR<cut>" for every cut, "ARs", "ARm", "ARl"} x 100, NaN when undefined.  Per
+    area range and cut: recall[t] = sum_b tp / sum_b npig (-1 when no image has a non-ignored ground truth), the mean of the entries > -1.
+    The AR<cut> keys are area `all`; ARs / ARm / ARl are read at the last cut.  (`accumulate`'s recall is the cumulative tp's last column
+    over npig: the sum of the images' counts.)"""
+    areas = list(AREA_RNG)
+    npig = np.asarray(stats["npig"]).sum(axis=1)
+
+    def ar(a, m):
+        rec = stats["tp"][a, :, :, m].sum(axis=0, dtype=np.int64).astype(np.float64) / npig[a] if npig[a] > 0 else -np.ones(len(IOU_THRS))
+        v = _mean(rec)
+        return v * 100 if v >= 0 else float("nan")
+    out = {f"AR{c}": ar(areas.index("all"), m) for m, c in enumerate(stats["cuts"])}
+    out.update({k: ar(areas.index(a), len(stats["cuts"]) - 1) for k, a in (("ARs", "small"), ("ARm", "medium"), ("ARl", "large"))})
+    return out
+
+
+def image_rows(stats, count_gt, count_pred):
+    """One dict per image: image_id, count_gt, count_pred, diff = count_gt - count_pred (the sign of L2/scripts/analyze_res.py), AP / AP50 / AP75 /
+    APs / APm / APl of the image alone (x 100; NaN where it has no non-ignored ground truth in that range), tp50 / fp50 / fn50 (area `all`, IoU
+    0.5, the last cut; fn50 = npig - tp50).  count_gt / count_pred: {image_id: count}, the rows following count_gt's order (an image the
+    statistics left out -- neither ground truth nor detection -- gets NaN and zeros), or sequences beside stats["image_ids"]."""
+    areas = list(AREA_RNG)
+    ids = list(count_gt) if isinstance(count_gt, dict) else list(stats["image_ids"])
+    if not isinstance(count_gt, dict):
+        count_gt, count_pred = dict(zip(ids, count_gt)), dict(zip(ids, count_pred))
+    at = {i: b for b, i in enumerate(stats["image_ids"])}
+    t50, t75, last = int(np.argmax(np.isclose(IOU_THRS, 0.5))), int(np.argmax(np.isclose(IOU_THRS, 0.75))), len(stats["cuts"]) - 1
+    pct = lambda v: v * 100 if v >= 0 else float("nan")                    # noqa: E731
+    rows = []
+    for i in ids:
+        row = {"image_id": i, "count_gt": int(count_gt[i]), "count_pred": int(count_pred[i]), "diff": int(count_gt[i]) - int(count_pred[i])}
+        b = at.get(i)
+        if b is None:
+            row.update({k: float("nan") for k in ("AP", "AP50", "AP75", "APs", "APm", "APl")}, tp50=0, fp50=0, fn50=0)
+        else:
+            ap = stats["ap"]
+            a = areas.index("all")
+            row.update({"AP": pct(_mean(ap[a, b])), "AP50": pct(float(ap[a, b, t50])), "AP75": pct(float(ap[a, b, t75])),
+                        "APs": pct(_mean(ap[areas.index("small"), b])), "APm": pct(_mean(ap[areas.index("medium"), b])),
+                        "APl": pct(_mean(ap[areas.index("large"), b]))})
+            tp50 = int(stats["tp"][a, b, t50, last])
+            row.update(tp50=tp50, fp50=int(stats["fp"][a, b, t50, last]), fn50=int(stats["npig"][a, b]) - tp50)
+        rows.append(row)
+    return rows
+
+
+def image_report(stats, image_ids, count_gt, count_pred, split, threshold):
+    """What infer.py --image_report writes to image_report_<split>.json: {"split", "threshold", "max_dets", "AR" (`average_recall`), "rows"
+    (`image_rows`, in the order `image_ids` = the order the images were run), "order_by_ap" (image ids by ascending AP, NaN last, ties by id),
+    "order_by_diff" (image ids by descending diff, ties by id)}."""
+    rows = image_rows(stats, dict(zip(image_ids, count_gt)), dict(zip(image_ids, count_pred)))
+    by_ap = sorted(rows, key=lambda r: (r["AP"] != r["AP"], 0.0 if r["AP"] != r["AP"] else r["AP"], r["image_id"]))
+    by_diff = sorted(rows, key=lambda r: (-r["diff"], r["image_id"]))
+    return {"split": split, "threshold": float(threshold), "max_dets": list(stats["cuts"]), "AR": average_recall(stats), "rows": rows,
+            "order_by_ap": [r["image_id"] for r in by_ap], "order_by_diff": [r["image_id"] for r in by_diff]}
 
 
 def gt_from_json(gt_json, ids):

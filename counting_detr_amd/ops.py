@@ -2020,12 +2020,13 @@ def box_iou_xywh(dt, gt):
     return iou
 
 
-def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, iou_thrs, area_rng, g_max, host=False, events=None):
+def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, iou_thrs, area_rng, g_max, host=False, events=None, keep=None):
     """cdetr_coco_match: COCOeval's greedy matcher for B packed images x A area ranges x T IoU thresholds in one launch (device tensors:
     float64 boxes [*, 4] / areas / thresholds [T] / ranges [A, 2], uint8 ignore flags, int32 offset tables [B + 1]; detections in evaluation
     order; g_max = the largest ground-truth count of one image, known on the host).  -> matched [A, T, D], det_ignored [A, T, D] (uint8),
     npig [A, B] (int32): views of ONE byte buffer; host=True returns them as numpy arrays (bool, bool, int32) after a single copy.
-    events: a pair of torch.cuda.Event recorded right before / after the launch (tools/coco_ap_time.py)."""
+    events: a pair of torch.cuda.Event recorded right before / after the launch (tools/coco_ap_time.py).
+    keep: a list that receives the three device views as well when host=True (coco_image_stats reads them without a host trip)."""
     from ._ffi import CocoMatchDesc
     dev = gt_off.device
     B, T, A = gt_off.numel() - 1, iou_thrs.numel(), area_rng.numel() // 2
@@ -2046,11 +2047,46 @@ def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, 
     d.matched, d.det_ignored, d.npig = buf.data_ptr(), buf.data_ptr() + n_flag, buf.data_ptr() + n_pad
     with _between(events):
         check(lib().cdetr_coco_match(C.byref(d), stream_ptr()), "cdetr_coco_match")
+    views = buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
     if host:
+        if keep is not None:
+            keep.extend(views)
         h = buf.cpu().numpy()
         return (h[:n_flag].reshape(A, T, D).astype(bool), h[n_flag:2 * n_flag].reshape(A, T, D).astype(bool),
                 h[n_pad:].view("int32").reshape(A, B))
-    return buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
+    return views
+
+
+def coco_image_stats(matched, det_ignored, dt_off, npig, cuts, rec_thrs, dt_cnt=None, host=False, events=None):
+    """cdetr_coco_image_stats: per (area range, image, IoU threshold) the true / false positives at every maxDets cut and the image's own
+    average precision, from the flags of coco_match(host=False) as they lie in device memory (device tensors: uint8 matched / det_ignored
+    [A, T, D], int32 dt_off [B + 1], npig [A, B], cuts [M], dt_cnt [B] or None = whole segments; float64 rec_thrs [R]).
+    -> tp [A, B, T, M], fp [A, B, T, M] (int32), ap [A, B, T] (float64): views of ONE byte buffer; host=True returns them as numpy arrays
+    after a single copy.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/image_report_time.py)."""
+    _expect("coco_image_stats", torch.uint8, matched=matched, det_ignored=det_ignored)
+    _expect("coco_image_stats", torch.int32, dt_off=dt_off, npig=npig, cuts=cuts, dt_cnt=dt_cnt)
+    _expect("coco_image_stats", torch.float64, rec_thrs=rec_thrs)
+    if matched.dim() != 3 or matched.shape != det_ignored.shape or npig.dim() != 2 or npig.shape[0] != matched.shape[0] \
+            or dt_off.numel() != npig.shape[1] + 1 or (dt_cnt is not None and dt_cnt.numel() != npig.shape[1]):
+        raise RuntimeError(f"coco_image_stats: flags [A, T, D], dt_off [B + 1], npig [A, B], dt_cnt [B] expected, got {tuple(matched.shape)}, "
+                           f"{tuple(det_ignored.shape)}, {tuple(dt_off.shape)}, {tuple(npig.shape)}, {None if dt_cnt is None else tuple(dt_cnt.shape)}")
+    dev = dt_off.device
+    for name, t in (("matched", matched), ("det_ignored", det_ignored), ("npig", npig), ("cuts", cuts), ("rec_thrs", rec_thrs), ("dt_cnt", dt_cnt)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"coco_image_stats: `{name}` on {t.device}, dt_off on {dev}")
+    (A, T, D), B, M, R = matched.shape, npig.shape[1], cuts.numel(), rec_thrs.numel()
+    n_cnt = A * B * T * M
+    buf = torch.zeros(8 * A * B * T + 8 * n_cnt, dtype=torch.uint8, device=dev)           # ap first: float64 wants the 8-byte alignment
+    ap, tp, fp = buf[:8 * A * B * T].view(torch.float64), buf[8 * A * B * T:][:4 * n_cnt].view(torch.int32), buf[8 * A * B * T + 4 * n_cnt:].view(torch.int32)
+    with _between(events):
+        check(lib().cdetr_coco_image_stats(ptr(matched) if D else None, ptr(det_ignored) if D else None, ptr(dt_off), ptr(dt_cnt), ptr(npig),
+                                           ptr(cuts), ptr(rec_thrs), B, A, T, D, M, R, ptr(tp), ptr(fp), ptr(ap), stream_ptr()),
+              "cdetr_coco_image_stats")
+    if host:
+        h = buf.cpu().numpy()
+        ap, tp, fp = h[:8 * A * B * T].view("float64"), h[8 * A * B * T:][:4 * n_cnt].view("int32"), h[8 * A * B * T + 4 * n_cnt:].view("int32")
+        return tp.reshape(A, B, T, M), fp.reshape(A, B, T, M), ap.reshape(A, B, T)
+    return tp.view(A, B, T, M), fp.view(A, B, T, M), ap.view(A, B, T)
 
 
 def image_prep(raw, events=None):

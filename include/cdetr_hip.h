@@ -543,6 +543,35 @@ typedef struct {
 int cdetr_box_iou_xywh(const double* dt, int32_t D, const double* gt, int32_t G, double* iou, void* stream);
 int cdetr_coco_match(const cdetr_coco_match_desc* d, void* stream);
 
+/* ---- per-image evaluation statistics (csrc/coco_report.hip; infer.py --image_report): what the reference's evaluator keeps per image
+ * (A2/eval_all.py:181, 227-239: count and an `ap` field per image) and the counts behind COCOeval's recall numbers at maxDets 900 / 1000 /
+ * 1100, from the flags cdetr_coco_match left in device memory.  FLOAT64 and integers only, contraction into FMAs switched off: every output
+ * EQUALS coco_ap.stats_from_flags (numpy) bit for bit.
+ * cdetr_coco_image_stats: ONE launch, one workgroup per (image, area range), one wave per IoU threshold.  For (a, b, t) let n be the used
+ *   length of image b's segment dt_off[b] .. dt_off[b+1] (the whole segment, or min(dt_cnt[b], segment) with dt_cnt), and over its detections
+ *   i in order ctp_i / cfp_i the running counts of `matched & !ignored` / `!matched & !ignored`:
+ *     tp / fp [a][b][t][m] = ctp / cfp at index min(cuts[m], n) - 1, 0 when that length is 0.  COCOeval matches once over dt[:maxDets[-1]] and
+ *                            slices afterwards, and a greedy match never looks ahead: these ARE the counts of an evaluation at maxDet = cuts[m].
+ *     ap [a][b][t]         = -1.0 when npig[a][b] == 0; else with rc_i = ctp_i / npig, pr_i = ctp_i / ((cfp_i + ctp_i) + 2^-52) made
+ *                            non-increasing from the right and q[r] = pr[first i with rc_i >= rec_thrs[r]] (0 if there is none):
+ *                            (((q[0] + q[1]) + q[2]) + ...) / R, summed in index order by one lane.  n == 0 with npig > 0 gives 0.
+ *   Running counts are ballots and popcounts over chunks of 64 detections, the envelope a suffix maximum, a sample's index a search in the
+ *   one chunk whose recalls straddle it; no atomics, no floating-point value crosses lanes except through max.
+ *   Limits: T <= 16, M <= 64, R <= 256, A <= 65535, CDETR_ERR_UNSUPPORTED beyond, before any launch.  Detections per image: NO limit -- an
+ *   image is streamed in chunks of 64 and nothing per detection is held on chip (1100 at T = 10, the evaluator's maxDets, is 18 chunks).
+ *   rec_thrs need not be sorted; a cut <= 0 keeps nothing.  A segment that does not lie inside 0 .. Dtot counts as empty and is not read.
+ *   B == 0: nothing is launched.  Dtot == 0: the flag pointers may be NULL; the outputs are still written (zeros, -1 where npig is 0).      */
+int cdetr_coco_image_stats(const uint8_t* matched, const uint8_t* det_ignored,   /* [A][T][Dtot], cdetr_coco_match's outputs, device */
+                           const int32_t* dt_off,      /* [B+1] */
+                           const int32_t* dt_cnt,      /* [B] or NULL: use only the first min(dt_cnt[b], segment length) detections of image b */
+                           const int32_t* npig,        /* [A][B] */
+                           const int32_t* cuts,        /* [M] ascending maxDets cuts */
+                           const double* rec_thrs,     /* [R] */
+                           int32_t B, int32_t A, int32_t T, int32_t Dtot, int32_t M, int32_t R,
+                           int32_t* tp, int32_t* fp,   /* [A][B][T][M] */
+                           double* ap,                 /* [A][B][T] */
+                           void* stream);
+
 /* ---- image batches prepared on the device (csrc/image_prep.hip): what the reference's readers do per image on the host -- PIL resize,
  * ToTensor + Normalize (A2/data/fsc147.py:22-24, 75-77) -- plus this build's zero-padding to the batch maximum and its padding mask
  * (counting_detr_amd/data.py collate), in ONE launch, BIT-EQUAL to that host path.

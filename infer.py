@@ -28,8 +28,17 @@ the device path the store is emitted at the lowest threshold, one cdetr_count_sw
 gives every threshold's AP (the detections kept at a higher threshold are a prefix of the evaluation order: coco_ap.accumulate_sweep); on
 the host path the same report comes from numpy and coco_ap.summarize_sweep, the slow checker.
 
+`--image_report` says on WHICH images the model fails (the per-image list the reference's evaluator pickles, A2/eval_all.py:227-239, with the `ap`
+field its line 181 left empty, and COCOeval's six recall numbers beside the six AP): the metrics gain AR900 / AR1000 / AR1100 / ARs / ARm / ARl
+and image_report_<split>.json appears beside the predictions file ({"split", "threshold", "max_dets", "AR", "rows", "order_by_ap",
+"order_by_diff"}; a row = image_id, count_gt, count_pred, diff, the image's own AP / AP50 / AP75 / APs / APm / APl, tp50 / fp50 / fn50).  On the
+device path the flags of the split's one matching go through ONE cdetr_coco_image_stats launch where they lie; every other run forms the
+same numbers from the written predictions (coco_ap.image_stats; `--ap_on_host`: its host code, the checker).  With --sweep_thresholds the
+report describes the run's own --threshold.  Without the flag nothing changes.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --sweep_thresholds 0.3:0.7:9
   python infer.py -dp /data/FSC147 --split test --resume out/detr_retrain.pth -o out --device_detections --threshold ckpt
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --eval_batch_size 16
@@ -47,9 +56,37 @@ from counting_detr_amd.engine import count_from_logits, counting_metrics
 from counting_detr_amd.misc import NestedTensor
 
 
+class ImageReport:
+    """--image_report for one pass: where the box ground truth is, where the host route matches (`device`: a CUDA device, or None = coco_ap's
+    interpreted host code) and, after the pass, `report` = coco_ap.image_report's dict (None for a pass without images)."""
+
+    def __init__(self, gt_json, device=None):
+        self.gt_json, self.device, self.split, self.report = gt_json, device, None, None
+
+    def fill(self, stats, image_ids, gt_counts, pred_counts, threshold):
+        from counting_detr_amd.coco_ap import image_report
+        self.report = image_report(stats, image_ids, gt_counts, pred_counts, self.split, threshold)
+        return self.report["AR"]
+
+    def from_predictions(self, predictions, image_ids, gt_counts, pred_counts, threshold):
+        """The route of every pass whose detections are not matched from the device store: coco_ap.image_stats on the annotations of the
+        predictions file as written (`ap_from_json`'s reading of them)."""
+        from counting_detr_amd.coco_ap import image_stats
+        dt_by = {}
+        for a in predictions["annotations"]:
+            b = reference_box(a["bbox"])
+            dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
+        return self.fill(image_stats(gt_from_json(self.gt_json, image_ids), dt_by, device=self.device), image_ids, gt_counts, pred_counts, threshold)
+
+    def write(self, output_dir):
+        if self.report is not None:
+            with open(os.path.join(output_dir, "image_report_" + self.split + ".json"), "w") as handle:
+                json.dump(self.report, handle)
+
+
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True, sweep=None):
+          per_image=False, engine=None, write_json=True, sweep=None, image_report=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -63,11 +100,16 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     `threshold`: rounded to fp32 once (threshold_sweep.widen), the rule everywhere below.  `sweep` (a threshold_sweep.Sweep whose thresholds
     include `threshold`): the same pass also forms the counts of every image at every threshold of the sweep -- and, with `sweep.gt_json`, the
     six AP numbers per threshold --, leaves them in `sweep.report` / `sweep.counts` and writes threshold_sweep_<split>.json; the returned
-    metrics and the predictions file are those of a pass without it."""
+    metrics and the predictions file are those of a pass without it.
+    `image_report` (an ImageReport): the metrics gain the six average-recall keys and image_report_<split>.json is written wherever the
+    predictions file is; with `device_detections` and `gt_json` the statistics come from the store's ONE matching (one more launch),
+    otherwise from the predictions as written."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
     if sweep is not None:
         ts.column(sweep.thresholds, threshold)              # raises unless the run's own threshold is one of the sweep's
+    if image_report is not None:
+        image_report.split, image_report.report = split, None
     output_path = os.path.join(output_dir, "predictions_" + split + ".json") if write_json else None
     if output_path is not None and os.path.isfile(output_path):
         os.remove(output_path)
@@ -81,8 +123,10 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     elif getattr(engine, "trainer", None) is not None:
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
-        out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep)
+        out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report)
         _write_sweep(sweep, output_dir, split)
+        if image_report is not None and output_path is not None:
+            image_report.write(output_dir)
         return out
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
@@ -157,6 +201,10 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         sweep.counts = np.concatenate(tables)
         sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows)
     _write_sweep(sweep, output_dir, split)
+    if image_report is not None and n_img:
+        metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
+        if output_path is not None:
+            image_report.write(output_dir)
     return metrics, predictions
 
 
@@ -177,7 +225,7 @@ def _num_images(data_loader):
     raise RuntimeError("infer: device_detections needs the number of images up front (a DataLoader, a data.Prefetcher or a list of batches)")
 
 
-def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None):
+def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -187,11 +235,13 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     `sweep`: the store is emitted at the sweep's LOWEST threshold and one cdetr_count_sweep call per batch (ops.ThresholdSweep) sits beside the
     emit; after the loop one more copy brings the [N, T] table.  The file takes the wire records with score >= `threshold` (query order, ids
     from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, and the AP of every threshold comes
-    from ONE matching (coco_ap.summarize_store_sweep), the returned six numbers being its row at `threshold`."""
+    from ONE matching (coco_ap.summarize_store_sweep), the returned six numbers being its row at `threshold`.
+    `image_report` with `gt_json`: that one matching's flags also go through cdetr_coco_image_stats where they lie (with a sweep: the prefix
+    of every image that `threshold` keeps, min(its count there, max_det)); without `gt_json` the report is formed from the predictions dict."""
     import numpy as np
     from counting_detr_amd import ops
     from counting_detr_amd import threshold_sweep as ts
-    from counting_detr_amd.coco_ap import MAX_DETS, summarize_store, summarize_store_sweep
+    from counting_detr_amd.coco_ap import MAX_DET_CUTS, MAX_DETS, summarize_store, summarize_store_sweep
     if device.type != "cuda":
         raise RuntimeError(f"infer: device_detections runs HIP kernels, device={device} has none (the default is the host path)")
     N = _num_images(data_loader)
@@ -265,15 +315,31 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
         if n_img:
             metrics.update(counting_metrics(pred_counts, gt_counts))
         metrics["images"] = n_img
+        from_store = image_report is not None and gt_json is not None         # the statistics ride on the store's one matching
+        stats = None
         if sweep is not None and n_img:
             ap_json, ap_rows = sweep.gt_json if sweep.gt_json is not None else gt_json, None
             if ap_json is not None:
-                ap_rows = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds)
+                if from_store:
+                    at_threshold = np.minimum(sweep.counts[:, col], MAX_DETS)
+                    ap_rows, stats = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds,
+                                                           report=(MAX_DET_CUTS, at_threshold))
+                else:
+                    ap_rows = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds)
                 if gt_json is not None:
                     metrics.update(ap_rows[col])
             sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
+        elif from_store and n_img:
+            six, stats = summarize_store(gt_from_json(gt_json, image_ids), store, image_ids, report=(MAX_DET_CUTS, None))
+            metrics.update(six)
         elif gt_json is not None and n_img:
             metrics.update(summarize_store(gt_from_json(gt_json, image_ids), store, image_ids))
+        if stats is not None:
+            metrics.update(image_report.fill(stats, image_ids, gt_counts, pred_counts, threshold))
+        elif image_report is not None and n_img:
+            if predictions is None:
+                raise RuntimeError("infer: an image report without the device matching (gt_json) is formed from the predictions file: write_json=False")
+            metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
     return metrics, predictions
 
 
@@ -340,19 +406,36 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
     threshold = run_threshold(args)
     if sweep is None:
         sweep = build_sweep(args)
+    report = build_image_report(args, device)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
-                       sweep=sweep)
+                       sweep=sweep, image_report=report)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
         ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None
+        ar = {k: metrics.pop(k) for k in (report.report["AR"] if report is not None and report.report else ())}      # the AR keys follow the AP keys
         metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
+        metrics.update(ar)
     return metrics
+
+
+def build_image_report(args, device=None):
+    """--image_report -> an ImageReport for one pass, or None without the flag.  The report needs the split's box ground truth: a missing
+    instances_<split>.json is an error here, before anything runs.  `device`: where a pass that does not match from the device store forms
+    its statistics (a CUDA device unless --ap_on_host)."""
+    if not getattr(args, "image_report", False):
+        return None
+    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+    if not os.path.isfile(gt_json):
+        raise FileNotFoundError(f"--image_report needs the split's box ground truth: {gt_json} is not there")
+    on_device = device is not None and torch.device(device).type == "cuda" and not getattr(args, "ap_on_host", False)
+    return ImageReport(gt_json, torch.device(device) if on_device else None)
 
 
 def main(args):
     device = torch.device(args.device)
+    build_image_report(args)                                            # --image_report without instances_<split>.json: an error before anything is built
     model, criterion, _ = counting_detr_amd.build_model(args)
     model.to(device)
     if args.resume:

@@ -14,6 +14,7 @@ epoch's log line gains test_<k>, and --keep_best {mae,ap,loss} also saves the be
 --threshold T / --sweep_thresholds SPEC reach that pass and --eval (infer.py); with --calibrate_threshold {mae,rmse,nae,sre,ap} the sweep's best
 threshold follows the test_* keys as test_best_threshold / test_best_<metric> (the test_* keys themselves stay at --threshold) and every checkpoint
 written from then on carries "count_threshold": {"metric", "threshold", "value", "epoch"}, which `infer.py --threshold ckpt` reads.
+--image_report reaches the same passes (infer.py): six average-recall keys behind the AP keys, image_report_<split>.json wherever the predictions file is written.
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --synthetic --no_aux_loss ...
@@ -82,6 +83,9 @@ class Validator:
 def main(args):
     utils.init_distributed_mode(args)
     os.makedirs(args.output_dir, exist_ok=True)
+    if getattr(args, "image_report", False) and not args.synthetic and (args.eval or args.eval_every > 0):
+        import infer as _infer
+        _infer.build_image_report(args)         # without instances_<split>.json: an error now, not after the epochs
     device = torch.device(args.device if not getattr(args, "distributed", False) else f"cuda:{args.gpu}")
     # every rank builds the SAME initial weights (the init draws from the global RNG); only the data order is rank-specific.
     # Trainer additionally broadcasts rank 0's parameters and buffers (what DistributedDataParallel does at construction).
@@ -194,7 +198,7 @@ def main(args):
             gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
             metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=_infer.run_threshold(args),
                                       device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
-                                      per_image=per_image, sweep=_infer.build_sweep(args))
+                                      per_image=per_image, sweep=_infer.build_sweep(args), image_report=_infer.build_image_report(args, device))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
