@@ -4,7 +4,7 @@ import argparse
 
 
 def get_args_parser():
-    p = argparse.ArgumentParser("Counting-DETR 2nd stage (MI355X)", add_help=True)
+    p = _CheckedParser("Counting-DETR 2nd stage (MI355X)", add_help=True)
     p.add_argument("-dp", "--data_path", type=str, default="./FSC147/")
     p.add_argument("-o", "--output_dir", type=str, default="./outputs/anchor_detr")
     p.add_argument("-ts", "--test_split", type=str, default="val", choices=["val_PartA", "val_PartB", "test_PartA", "test_PartB", "test", "val"])
@@ -125,7 +125,44 @@ def get_args_parser():
                         "predictions file (per image: counts, diff, its own AP numbers, tp / fp / fn at IoU 0.5; the images ordered by AP and by "
                         "diff) and six average-recall keys (AR900, AR1000, AR1100, ARs, ARm, ARl) in the metrics.  Needs instances_<split>.json.  "
                         "With --device_detections: one cdetr_coco_image_stats launch on the flags of the split's one matching")
+    # the two below: no attribute when they are not given; both need --image_report (checked when the command line is parsed)
+    p.add_argument("--render_worst", default=argparse.SUPPRESS, type=int, metavar="K",
+                   help="infer.py / main.py --eval / --eval_every, with --image_report: draw the K images of lowest AP and the K of largest count "
+                        "error -- render_<split>/<image_id>.png (detections green = true positive at IoU 0.5, red = false positive, grey = ignored, "
+                        "with centre dots; ground truths blue, exemplars yellow) and render_<split>/index.json, beside the predictions file.  On "
+                        "a CUDA device one cdetr_render_boxes launch; --ap_on_host: the host painter, the same bytes")
+    p.add_argument("--render_ids", default=argparse.SUPPRESS, type=_id_list, metavar="ID,ID",
+                   help="with --image_report: also draw the images with these ids (a comma list); usable without --render_worst")
     return p
+
+
+class _CheckedParser(argparse.ArgumentParser):
+    """The 2nd-stage parser with the checks that span two flags: they fail when the command line is parsed, before anything is built."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        check_render_flags(ns, self.error)
+        return ns, rest
+
+
+def check_render_flags(ns, fail=None):
+    """--render_worst / --render_ids draw what --image_report lists: without it the run stops at start-up."""
+    given = [f for f in ("render_worst", "render_ids") if hasattr(ns, f)]
+    if given and not getattr(ns, "image_report", False):
+        msg = " / ".join("--" + f for f in given) + " needs --image_report: the images to draw are chosen from its report"
+        if fail is None:
+            raise ValueError(msg)
+        fail(msg)
+    if hasattr(ns, "render_worst") and ns.render_worst < 0:
+        msg = f"--render_worst must not be negative, got {ns.render_worst}"
+        if fail is None:
+            raise ValueError(msg)
+        fail(msg)
+
+
+def _id_list(text):
+    """--render_ids: `3,17` -> [3, 17]."""
+    return [int(t) for t in text.split(",") if t.strip()]
 
 
 def _threshold(text):

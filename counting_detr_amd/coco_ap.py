@@ -332,15 +332,17 @@ def pack_store(gt_by_img, store, image_ids):
             "dt_score": np.ascontiguousarray(score), "dt_off": np.concatenate([[0], np.cumsum([n_dt(i) for i in ids])]).astype(np.int32)}
 
 
-def _store_flags(gt_by_img, store, image_ids, device, max_det, report):
+def _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept=None):
     """The shared head of `summarize_store` / `summarize_store_sweep`: the store's pack and the flags of its ONE cdetr_coco_match launch on the
     host -> (pack, matched, ignored, npig, stats); `report` = (cuts, counts) also runs cdetr_coco_image_stats on the flags where the launch
-    left them (`stats`: the dict of `image_stats`, else None).  counts[k] belongs to the store's image k."""
+    left them (`stats`: the dict of `image_stats`, else None).  counts[k] belongs to the store's image k.  `kept`: a dict that receives what a
+    later reader of the same matching needs (render.py's overlays): "pack", "flags" = the launch's three device tensors (empty without an
+    image), "counts" = `counts` per image of the pack, or None."""
     if store.max_det != max_det:
         raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
     device = store.buf.device if device is None else _cuda(device)
     pack = pack_store(gt_by_img, store, image_ids)
-    keep = [] if report is not None else None
+    keep = [] if report is not None or kept is not None else None
     matched, ignored, npig = match_on_device(pack, device, tuple(AREA_RNG), keep=keep)
     stats = None
     if report is not None:
@@ -348,6 +350,8 @@ def _store_flags(gt_by_img, store, image_ids, device, max_det, report):
         if counts is not None:
             slot = {int(i): k for k, i in enumerate(image_ids)}
             counts = [int(counts[slot[i]]) if i in slot else 0 for i in pack["image_ids"]]
+        if kept is not None:
+            kept.update(pack=pack, flags=keep, counts=counts)
         if keep:
             stats = _stats_on_device(pack, keep, cuts, counts, npig, device)
         else:                                                              # no image at all: nothing was launched
@@ -355,13 +359,14 @@ def _store_flags(gt_by_img, store, image_ids, device, max_det, report):
     return pack, matched, ignored, npig, stats
 
 
-def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS, report=None):
+def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS, report=None, kept=None):
     """`summarize(..., device=)` for an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections): the same six numbers
     as `ap_from_json(device=)` gives on the predictions json written from that store, without the json trip -- the evaluation records go to
     cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image k; `gt_by_img` as for `summarize`
     (`gt_from_json`).  `device`: the store's own (default).
-    `report` = (cuts, counts): -> (the six numbers, the per-image statistics of `image_stats_store`) from the SAME matching launch."""
-    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report)
+    `report` = (cuts, counts): -> (the six numbers, the per-image statistics of `image_stats_store`) from the SAME matching launch; with it,
+    `kept` (a dict) receives the pack and the device flags of that launch (`_store_flags`)."""
+    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept)
     by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}
     return _six(by_area) if report is None else (_six(by_area), stats)
 
@@ -403,17 +408,17 @@ def summarize_flags_sweep(scores, flags, thresholds):
     return [_six({a: per_area[a][k] for a in per_area}) for k in range(len(thresholds))]
 
 
-def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS, report=None):
+def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS, report=None, kept=None):
     """`summarize_store` at every score threshold of `thresholds` from ONE cdetr_coco_match launch: the store was emitted at the lowest
     threshold (checked), the flags of every higher one are a prefix of what that launch returns (`accumulate_sweep`).  -> list of the six
     numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold.
     `report` = (cuts, counts): -> (that list, the per-image statistics of `image_stats_store`) from the same launch; counts[k] = the
-    detections of the store's image k that the threshold to be reported keeps (a prefix, as above)."""
+    detections of the store's image k that the threshold to be reported keeps (a prefix, as above); `kept`: as for `summarize_store`."""
     t32 = np.asarray(list(thresholds), dtype=np.float64).astype(np.float32)
     if len(t32) == 0 or np.isnan(t32).any() or np.float32(store.threshold) != t32.min():
         raise RuntimeError(f"coco_ap: a sweep over {t32.tolist()} needs a store emitted at its lowest threshold, this one was emitted at "
                            f"{store.threshold}")
-    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report)
+    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept)
     rows = summarize_flags_sweep(pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}, t32)
     return rows if report is None else (rows, stats)
 

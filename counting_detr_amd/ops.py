@@ -2089,6 +2089,55 @@ def coco_image_stats(matched, det_ignored, dt_off, npig, cuts, rec_thrs, dt_cnt=
     return tp.view(A, B, T, M), fp.view(A, B, T, M), ap.view(A, B, T)
 
 
+def render_boxes(pix, pix_off, size, sel, dt_boxes, dt_off, matched50, ignored50, gt_boxes, gt_off, ex_boxes, ex_off, style, dot=1, dt_cnt=None,
+                 sel_host=None, max_hw=None, out=None, events=None):
+    """cdetr_render_boxes: the box overlays of K canvases in one launch (counting_detr_amd/render.py states the rule).  Device tensors: uint8 pix
+    (the canvases' HWC bytes, concatenated), int64 pix_off [K + 1], int32 size [K, 2] = (H, W), sel [K] (the pack image a canvas shows), float64
+    dt_boxes [D, 4] in evaluation order with int32 dt_off [B + 1] and dt_cnt [B] or None (draw only the first dt_cnt[b]), uint8 matched50 /
+    ignored50 [D] (row [0, 0] of coco_match's outputs: area range `all`, IoU 0.5), float64 gt_boxes [G, 4] with gt_off [B + 1], ex_boxes [E, 4]
+    with ex_off [K + 1] (per canvas), uint8 style [5, 4].  sel_host: the host's copy of sel (checked against B before the launch); max_hw: the
+    largest (H, W), host-known -- both are read back from the device when left out.  -> out, uint8 laid out like pix, every byte written (an
+    `out` passed in needs pix.numel() bytes and no initialisation).  events: a pair of torch.cuda.Event recorded right before / after the launch
+    (tools/render_time.py)."""
+    _expect("render_boxes", torch.uint8, pix=pix, matched50=matched50, ignored50=ignored50, style=style, out=out)
+    _expect("render_boxes", torch.int64, pix_off=pix_off)
+    _expect("render_boxes", torch.int32, size=size, sel=sel, dt_off=dt_off, dt_cnt=dt_cnt, gt_off=gt_off, ex_off=ex_off)
+    _expect("render_boxes", torch.float64, dt_boxes=dt_boxes, gt_boxes=gt_boxes, ex_boxes=ex_boxes)
+    K, B = sel.numel(), dt_off.numel() - 1
+    D, G, E = dt_boxes.numel() // 4, gt_boxes.numel() // 4, ex_boxes.numel() // 4
+    if size.numel() != 2 * K or pix_off.numel() != K + 1 or ex_off.numel() != K + 1 or gt_off.numel() != B + 1 or style.numel() != 20 \
+            or matched50.numel() != D or ignored50.numel() != D or (dt_cnt is not None and dt_cnt.numel() != B) \
+            or dt_boxes.numel() != 4 * D or gt_boxes.numel() != 4 * G or ex_boxes.numel() != 4 * E:
+        raise RuntimeError(f"render_boxes: size [K, 2], pix_off / ex_off [K + 1], dt_off / gt_off [B + 1], flags [D], dt_cnt [B], style [5, 4] "
+                           f"expected for K = {K}, B = {B}, D = {D}, got {tuple(size.shape)}, {tuple(pix_off.shape)}, {tuple(ex_off.shape)}, "
+                           f"{tuple(dt_off.shape)}, {tuple(gt_off.shape)}, {tuple(matched50.shape)}, {tuple(ignored50.shape)}, "
+                           f"{None if dt_cnt is None else tuple(dt_cnt.shape)}, {tuple(style.shape)}")
+    dev = pix.device
+    for name, t in (("pix_off", pix_off), ("size", size), ("sel", sel), ("dt_boxes", dt_boxes), ("dt_off", dt_off), ("dt_cnt", dt_cnt),
+                    ("matched50", matched50), ("ignored50", ignored50), ("gt_boxes", gt_boxes), ("gt_off", gt_off), ("ex_boxes", ex_boxes),
+                    ("ex_off", ex_off), ("style", style), ("out", out)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"render_boxes: `{name}` on {t.device}, pix on {dev}")
+    if out is None:
+        out = torch.empty(pix.numel(), dtype=torch.uint8, device=dev)
+    elif out.numel() < pix.numel():
+        raise RuntimeError(f"render_boxes: `out` holds {out.numel()} bytes, the canvases {pix.numel()}")
+    if K and max_hw is None:
+        max_hw = tuple(int(v) for v in size.view(K, 2).max(dim=0).values.tolist())
+    if K and sel_host is None:
+        sel_host = sel.tolist()
+    max_h, max_w = max_hw if K else (1, 1)
+    host = (C.c_int32 * K)(*[int(s) for s in sel_host]) if K else None
+    with _between(events):
+        check(lib().cdetr_render_boxes(ptr(pix) if K else None, ptr(pix_off), ptr(size) if K else None, ptr(sel) if K else None, host,
+                                       ptr(dt_boxes) if D else None, ptr(dt_off), ptr(dt_cnt), ptr(matched50) if D else None,
+                                       ptr(ignored50) if D else None, ptr(gt_boxes) if G else None, ptr(gt_off), ptr(ex_boxes) if E else None,
+                                       ptr(ex_off), ptr(style), K, B, D, G, E, int(max_h), int(max_w), int(dot), pix.numel(), ptr(out) if K else None,
+                                       stream_ptr()),
+              "cdetr_render_boxes")
+    return out
+
+
 def image_prep(raw, events=None):
     """cdetr_image_prep: the `raw` part of a batch from data.collate_raw / collate_stage1_raw, already on the device (uint8 `pixels`, int32
     `images` records and `tables`, fp32 `lut` [3, 256]; ints Hm, Wm, max_taps, max_rows) -> (image fp32 [B, 3, Hm, Wm], mask bool [B, Hm, Wm]),

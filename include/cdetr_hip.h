@@ -572,6 +572,48 @@ int cdetr_coco_image_stats(const uint8_t* matched, const uint8_t* det_ignored,  
                            double* ap,                 /* [A][B][T] */
                            void* stream);
 
+/* ---- box overlays drawn on the device (csrc/render.hip; infer.py --render_worst / --render_ids): what the reference's evaluators draw with
+ * cv2.rectangle / cv2.circle under `visualize_res` and never save (L2/offline_lvis_evaluator.py:167-207), as ONE launch over the chosen images
+ * of a split, from the boxes and the IoU-0.5 flags cdetr_coco_match left in device memory.  Integers and float64 only, contraction into FMAs
+ * switched off: every byte EQUALS counting_detr_amd/render.py's host implementation (the rule is stated there).
+ * cdetr_render_boxes: canvas k (size[k] = {H, W}, its HWC bytes at pix + pix_off[k]) shows pack image b = sel[k]: its first
+ *   min(dt_cnt[b], segment) detections (the whole segment dt_off[b] .. dt_off[b+1] without dt_cnt), its ground truths gt_off[b] .. gt_off[b+1]
+ *   and the canvas's own exemplars ex_off[k] .. ex_off[k+1].  A box [x, y, w, h] has the integer corners x0 = floor(x), y0 = floor(y),
+ *   x1 = floor(x + w), y1 = floor(y + h), each clamped to [-2, 32768] in float64 before the conversion; a non-finite field, x1 < x0 or y1 < y0
+ *   draws nothing.  Its outline of thickness t: the canvas pixels inside the corners with min(px - x0, x1 - px, py - y0, y1 - py) < t.  A
+ *   detection also has a centre dot, the square |px - cx| <= dot, |py - cy| <= dot around cx = floor(x + w * 0.5), cy = floor(y + h * 0.5)
+ *   (dot < 0: none).  Detection i is `ignored` when det_ignored[i], else `tp` when matched[i], else `fp`.  A pixel takes the colour of the
+ *   FIRST primitive that covers it in the order: dots (evaluation order), detection outlines (evaluation order), ground truths, exemplars;
+ *   a pixel nothing covers keeps the image's.  EVERY byte of every canvas of `out` (laid out like pix) is written.
+ *   style: [5][4] bytes (r, g, b, thickness) for tp, fp, ignored, ground truth, exemplar.
+ *   One workgroup per (tile of CDETR_RENDER_TILE_H x _TILE_W pixels, canvas), the grid sized by max_h x max_w; a workgroup walks the
+ *   canvas's primitives in that order in chunks of CDETR_RENDER_CHUNK: one primitive per thread culled against the tile, the survivors
+ *   compacted in order into LDS (ballot + prefix), every pixel scanning them up to its first hit; it stops when all its pixels have one.
+ *   No atomics, one writer per byte.  Every table entry is range-checked on the device before it addresses anything (B, D, G, E,
+ *   pix_bytes): an inconsistent segment counts as empty, a canvas that does not lie inside pix_bytes or exceeds max_h / max_w is skipped.
+ *   Validation, before any launch: negative sizes or a NULL where data is required CDETR_ERR_ARG; K > 65535, max_h / max_w outside
+ *   1 .. 16384, a grid beyond 2^31 threads, dot > 16384 or an entry of sel_host (the caller's HOST copy of sel, may be NULL) outside
+ *   [0, B): CDETR_ERR_UNSUPPORTED.  K == 0: nothing is launched.  D / G / E == 0: their pointers may be NULL.                         */
+#define CDETR_RENDER_TILE_H 16
+#define CDETR_RENDER_TILE_W 16
+#define CDETR_RENDER_CHUNK 256
+int cdetr_render_boxes(const uint8_t* pix,          /* canvases, HWC bytes, concatenated; device */
+                       const int64_t* pix_off,      /* [K+1] byte offsets */
+                       const int32_t* size,         /* [K][2] = H, W */
+                       const int32_t* sel,          /* [K] pack image of canvas k */
+                       const int32_t* sel_host,     /* HOST copy of sel for the range check, or NULL */
+                       const double* dt_boxes,      /* [D][4] xywh, evaluation order */
+                       const int32_t* dt_off,       /* [B+1] */
+                       const int32_t* dt_cnt,       /* [B] or NULL */
+                       const uint8_t* matched, const uint8_t* det_ignored,   /* [D]: row (area all, IoU 0.5) of cdetr_coco_match's outputs */
+                       const double* gt_boxes,      /* [G][4] */
+                       const int32_t* gt_off,       /* [B+1] */
+                       const double* ex_boxes,      /* [E][4] */
+                       const int32_t* ex_off,       /* [K+1] */
+                       const uint8_t* style,        /* [5][4] */
+                       int32_t K, int32_t B, int32_t D, int32_t G, int32_t E, int32_t max_h, int32_t max_w, int32_t dot, int64_t pix_bytes,
+                       uint8_t* out, void* stream);
+
 /* ---- image batches prepared on the device (csrc/image_prep.hip): what the reference's readers do per image on the host -- PIL resize,
  * ToTensor + Normalize (A2/data/fsc147.py:22-24, 75-77) -- plus this build's zero-padding to the batch maximum and its padding mask
  * (counting_detr_amd/data.py collate), in ONE launch, BIT-EQUAL to that host path.

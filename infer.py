@@ -36,9 +36,21 @@ device path the flags of the split's one matching go through ONE cdetr_coco_imag
 same numbers from the written predictions (coco_ap.image_stats; `--ap_on_host`: its host code, the checker).  With --sweep_thresholds the
 report describes the run's own --threshold.  Without the flag nothing changes.
 
+`--render_worst K` / `--render_ids 3,17` (both need --image_report; an error at start-up otherwise) SHOW those images -- the step the reference's
+evaluators left half alive (`visualize_res` draws boxes, centres and ground truths with cv2 and its imwrite is commented out,
+L2/offline_lvis_evaluator.py:167-207): render_<split>/<image_id>.png for the K images of lowest AP, the K of largest count error and the ids named,
+and render_<split>/index.json ({"split", "threshold", "style", "dot", "images": [{"image_id", "file_name", "png", "reasons", "row"}]}), wherever the
+predictions file is written.  Detections are green (true positive at IoU 0.5), red (false positive) or grey (ignored) with a centre dot, ground
+truths blue, exemplars yellow; counting_detr_amd/render.py states the integer rule.  `--ap_on_host` draws with its numpy implementation from the
+written predictions and the host matcher's flags (the checker); any other host-loop run matches the predictions on the device and draws there; with
+`--device_detections` ONE cdetr_render_boxes launch reads the store's boxes and the flags of the split's one matching where they lie -- only the
+chosen images' pixels go up, only the overlays come back.  Same PNG bytes on every route.  Without the flags nothing changes.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_worst 8
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_ids 3,17
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --sweep_thresholds 0.3:0.7:9
   python infer.py -dp /data/FSC147 --split test --resume out/detr_retrain.pth -o out --device_detections --threshold ckpt
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --eval_batch_size 16
@@ -72,10 +84,7 @@ class ImageReport:
         """The route of every pass whose detections are not matched from the device store: coco_ap.image_stats on the annotations of the
         predictions file as written (`ap_from_json`'s reading of them)."""
         from counting_detr_amd.coco_ap import image_stats
-        dt_by = {}
-        for a in predictions["annotations"]:
-            b = reference_box(a["bbox"])
-            dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
+        dt_by = _detections_as_written(predictions)
         return self.fill(image_stats(gt_from_json(self.gt_json, image_ids), dt_by, device=self.device), image_ids, gt_counts, pred_counts, threshold)
 
     def write(self, output_dir):
@@ -84,9 +93,69 @@ class ImageReport:
                 json.dump(self.report, handle)
 
 
+def _detections_as_written(predictions):
+    """{image_id: [detections]} of a predictions dict, as `coco_ap.ap_from_json` reads the file: the evaluation boxes the matcher sees."""
+    dt_by = {}
+    for a in predictions["annotations"]:
+        b = reference_box(a["bbox"])
+        dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
+    return dt_by
+
+
+class Render:
+    """--render_worst K / --render_ids for one pass: the overlays of the images `render.select` picks from the pass's image report, written to
+    render_<split>/ wherever the predictions file is (counting_detr_amd/render.py states the drawing rule).  `out_dir`: where the last pass
+    wrote them (None: it wrote none)."""
+
+    def __init__(self, data_path, worst=0, ids=()):
+        self.data_path, self.worst, self.ids, self.out_dir = data_path, int(worst), tuple(ids), None
+
+    def from_predictions(self, predictions, image_ids, image_report, output_dir, threshold):
+        """The route of every pass whose detections are not matched from the device store: the predictions as written are packed and
+        matched again at area range `all` -- `image_report.device` None (--ap_on_host): coco_ap's host matcher and render.py's host
+        implementation, the checker; a CUDA device: one cdetr_coco_match launch whose flags stay there, one cdetr_render_boxes launch."""
+        import numpy as np
+        from counting_detr_amd import coco_ap as ca
+        gt_by, dt_by = gt_from_json(image_report.gt_json, image_ids), _detections_as_written(predictions)
+        pack = ca.pack_images(gt_by, dt_by)
+        device, T = image_report.device, len(ca.IOU_THRS)
+        if device is None:
+            per = [ca._evaluate_image(dt_by.get(i, []), gt_by.get(i, []), ca.AREA_RNG["all"], ca.MAX_DETS) for i in pack["image_ids"]]
+            matched50 = np.concatenate([e[1].reshape(T, -1)[0] for e in per] + [np.zeros(0, dtype=bool)])
+            ignored50 = np.concatenate([e[2].reshape(T, -1)[0] for e in per] + [np.zeros(0, dtype=bool)])
+        else:
+            flags = []
+            ca.match_on_device(pack, device, ("all",), keep=flags, host=False)
+            matched50, ignored50 = (flags[0][0, 0], flags[1][0, 0]) if flags else (np.zeros(0, dtype=bool), np.zeros(0, dtype=bool))
+        return self.draw(pack, matched50, ignored50, None, device, image_report, output_dir, threshold)
+
+    def from_store(self, kept, device, image_report, output_dir, threshold):
+        """The route of --device_detections: `kept` = what the store's ONE matching left (coco_ap.summarize_store(kept=)): the boxes are read
+        from pack["dt_device"], the flags from the launch's tensors, the prefix lengths are the counts at the run's threshold."""
+        import numpy as np
+        flags = kept["flags"]
+        matched50, ignored50 = (flags[0][0, 0], flags[1][0, 0]) if flags else (np.zeros(0, dtype=bool), np.zeros(0, dtype=bool))
+        return self.draw(kept["pack"], matched50, ignored50, kept["counts"], device, image_report, output_dir, threshold)
+
+    def draw(self, pack, matched50, ignored50, dt_cnt, device, image_report, output_dir, threshold):
+        from counting_detr_amd import render as rd
+        report = image_report.report
+        picks = rd.select(report, self.worst, self.ids)
+        canvases, files, exemplars = rd.load_canvases(self.data_path, image_report.split, [p["image_id"] for p in picks])
+        at = {i: b for b, i in enumerate(pack["image_ids"])}
+        drawn = [k for k, p in enumerate(picks) if p["image_id"] in at]             # an image with neither ground truth nor detection is not packed
+        overlays = rd.render_images([canvases[k] for k in drawn], pack, matched50, ignored50, [at[picks[k]["image_id"]] for k in drawn], dt_cnt=dt_cnt,
+                                    exemplars=[exemplars[k] for k in drawn], device=device) if drawn else []
+        by_pick = dict(zip(drawn, overlays))
+        overlays = [by_pick[k] if k in by_pick else rd.paint_first_hit(canvases[k], *rd.primitives([], [], [], exemplars[k]))       # exemplars only
+                    for k in range(len(picks))]
+        self.out_dir = rd.write(output_dir, image_report.split, threshold, picks, files, report, overlays)
+        return self.out_dir
+
+
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True, sweep=None, image_report=None):
+          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -103,9 +172,15 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     metrics and the predictions file are those of a pass without it.
     `image_report` (an ImageReport): the metrics gain the six average-recall keys and image_report_<split>.json is written wherever the
     predictions file is; with `device_detections` and `gt_json` the statistics come from the store's ONE matching (one more launch),
-    otherwise from the predictions as written."""
+    otherwise from the predictions as written.
+    `render` (a Render; needs `image_report`): render_<split>/ with the overlays of the report's worst images is written wherever the
+    predictions file is, drawn where the pass matched: from the store's one matching, else from the predictions as written."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
+    if render is not None:
+        if image_report is None:
+            raise ValueError("infer: --render_worst / --render_ids draw what --image_report lists: pass an ImageReport as well")
+        render.out_dir = None
     if sweep is not None:
         ts.column(sweep.thresholds, threshold)              # raises unless the run's own threshold is one of the sweep's
     if image_report is not None:
@@ -123,7 +198,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     elif getattr(engine, "trainer", None) is not None:
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
-        out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report)
+        out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report,
+                            render, output_dir)
         _write_sweep(sweep, output_dir, split)
         if image_report is not None and output_path is not None:
             image_report.write(output_dir)
@@ -205,6 +281,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
         if output_path is not None:
             image_report.write(output_dir)
+            if render is not None:
+                render.from_predictions(predictions, image_ids, image_report, output_dir, threshold)
     return metrics, predictions
 
 
@@ -225,7 +303,8 @@ def _num_images(data_loader):
     raise RuntimeError("infer: device_detections needs the number of images up front (a DataLoader, a data.Prefetcher or a list of batches)")
 
 
-def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None):
+def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None,
+                  render=None, output_dir=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -237,7 +316,9 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, and the AP of every threshold comes
     from ONE matching (coco_ap.summarize_store_sweep), the returned six numbers being its row at `threshold`.
     `image_report` with `gt_json`: that one matching's flags also go through cdetr_coco_image_stats where they lie (with a sweep: the prefix
-    of every image that `threshold` keeps, min(its count there, max_det)); without `gt_json` the report is formed from the predictions dict."""
+    of every image that `threshold` keeps, min(its count there, max_det)); without `gt_json` the report is formed from the predictions dict.
+    `render` (with `output_path`): the overlays are drawn from what that matching left on the device -- the store's boxes, the flags, those
+    prefix lengths --, only the chosen images' pixels go up and only the overlays come back; without `gt_json`: from the predictions dict."""
     import numpy as np
     from counting_detr_amd import ops
     from counting_detr_amd import threshold_sweep as ts
@@ -317,20 +398,21 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
         metrics["images"] = n_img
         from_store = image_report is not None and gt_json is not None         # the statistics ride on the store's one matching
         stats = None
+        kept = {} if render is not None and from_store and output_path is not None else None
         if sweep is not None and n_img:
             ap_json, ap_rows = sweep.gt_json if sweep.gt_json is not None else gt_json, None
             if ap_json is not None:
                 if from_store:
                     at_threshold = np.minimum(sweep.counts[:, col], MAX_DETS)
                     ap_rows, stats = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds,
-                                                           report=(MAX_DET_CUTS, at_threshold))
+                                                           report=(MAX_DET_CUTS, at_threshold), kept=kept)
                 else:
                     ap_rows = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds)
                 if gt_json is not None:
                     metrics.update(ap_rows[col])
             sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
         elif from_store and n_img:
-            six, stats = summarize_store(gt_from_json(gt_json, image_ids), store, image_ids, report=(MAX_DET_CUTS, None))
+            six, stats = summarize_store(gt_from_json(gt_json, image_ids), store, image_ids, report=(MAX_DET_CUTS, None), kept=kept)
             metrics.update(six)
         elif gt_json is not None and n_img:
             metrics.update(summarize_store(gt_from_json(gt_json, image_ids), store, image_ids))
@@ -340,6 +422,11 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             if predictions is None:
                 raise RuntimeError("infer: an image report without the device matching (gt_json) is formed from the predictions file: write_json=False")
             metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
+        if render is not None and output_path is not None and image_report.report is not None:
+            if kept:
+                render.from_store(kept, device, image_report, output_dir, threshold)
+            else:
+                render.from_predictions(predictions, image_ids, image_report, output_dir, threshold)
     return metrics, predictions
 
 
@@ -407,9 +494,10 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
     if sweep is None:
         sweep = build_sweep(args)
     report = build_image_report(args, device)
+    render = build_render(args)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
-                       sweep=sweep, image_report=report)
+                       sweep=sweep, image_report=report, render=render)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
@@ -433,8 +521,19 @@ def build_image_report(args, device=None):
     return ImageReport(gt_json, torch.device(device) if on_device else None)
 
 
+def build_render(args):
+    """--render_worst K / --render_ids -> a Render for one pass, or None without either flag.  Both draw what --image_report lists: without
+    it this is an error (the parser says so first; a namespace built by hand meets it here)."""
+    if not hasattr(args, "render_worst") and not hasattr(args, "render_ids"):
+        return None
+    from counting_detr_amd.args import check_render_flags
+    check_render_flags(args)
+    return Render(args.data_path, getattr(args, "render_worst", 0), getattr(args, "render_ids", ()))
+
+
 def main(args):
     device = torch.device(args.device)
+    build_render(args)
     build_image_report(args)                                            # --image_report without instances_<split>.json: an error before anything is built
     model, criterion, _ = counting_detr_amd.build_model(args)
     model.to(device)
