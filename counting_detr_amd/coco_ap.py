@@ -21,27 +21,26 @@ PARITY UNPINNED: there is no pycocotools here to generate golden vectors from, a
 (`tests/test_coco_ap.py`) pin the restatement to hand-derived cases and to the invariants of the definition only.  It is host-side
 post-processing on a json pair -- not part of the step `bench.py` measures.
 
-DEVICE PATH (`device=` a CUDA device on box_iou_xywh / average_precision / summarize / ap_from_json; `device=None`, the default, is the host
-code below, untouched, and stays the checker): `pack_images` flattens all images into packed float64 arrays + offset tables (detections in
-evaluation order), ONE `cdetr_coco_match` launch (csrc/coco_eval.hip) matches every image under every area range and IoU threshold, the
-flags come back in one copy and `accumulate` forms `precision[T, R]` with array operations -- the same float64 operations in the same
-order as the loops of `average_precision`, so the two paths return EQUAL numbers (tests/test_coco_ap_device_cpu.py, _gpu.py).
+ONE MATCHING, MANY READERS (`Matching`): the flags of a matching -- matched, det_ignored [A, T, D], npig [A, B], images side by side in
+`pack_images` order -- are a value.  `Matching.of(gt, dt)` makes it with the host code below (`_evaluate_image`, untouched: the checker),
+`Matching.of(gt, dt, device)` / `Matching.launch(pack, device)` with ONE `cdetr_coco_match` launch (csrc/coco_eval.hip) whose flags stay on
+the device, `match_store` from an ops.DetectionStore (`pack_store` packs only the ground truths; the detections are read where
+cdetr_emit_detections, csrc/detections.hip, left them in evaluation order) and `match_predictions` from a predictions dict as written.  Its
+readings: `host()` (the flags in one copy, taken once), `six()` (`accumulate` = the tail of `average_precision` as array operations, the same
+float64 operations in the same order: EQUAL numbers), `six_sweep(thresholds)`, `stats(cuts, counts)` and `row50()` (render.py's overlays).
+`summarize(device=)`, `summarize_store`, `summarize_store_sweep`, `image_stats` and `image_stats_store` are one maker and one reading each
+(tests/test_matching_cpu.py, test_coco_ap_device_gpu.py, test_detections_gpu.py).
 
-STORE PATH (`summarize_store`): the detections never visit the host as dicts -- cdetr_emit_detections (csrc/detections.hip) left them in an
-ops.DetectionStore in evaluation order, `pack_store` packs only the ground truths and `match_on_device` reads the detections from device memory;
-the same launch, the same `accumulate`, EQUAL numbers again (tests/test_detections_gpu.py).
+SCORE-THRESHOLD SWEEP (`six_sweep`, infer.py --sweep_thresholds): the six numbers at several score thresholds from ONE matching at the lowest of
+them -- in evaluation order the detections a higher threshold keeps are a prefix, per image and after the merge, and a greedy match never
+looks ahead (`accumulate_sweep`).  `summarize_sweep` filters and evaluates once per threshold on the host: slow, and the
+checker (tests/test_threshold_sweep_cpu.py, _gpu.py).
 
-SCORE-THRESHOLD SWEEP (`summarize_store_sweep`, infer.py --sweep_thresholds): the six numbers at several score thresholds from ONE matching at
-the lowest of them -- in evaluation order the detections a higher threshold keeps are a prefix, per image and after the merge, and a greedy
-match never looks ahead (`accumulate_sweep`).  `summarize_sweep` filters and evaluates once per threshold on the host: slow,
-and the checker (tests/test_threshold_sweep_cpu.py, _gpu.py).
-
-PER-IMAGE STATISTICS (`image_stats`, `image_stats_store`, infer.py --image_report): the list the reference's evaluator keeps per image
-(A2/eval_all.py:227-239, its `ap` field left empty at line 181) and the counts behind COCOevalMaxDets.summarize's stats[6..11], AR at maxDets
-900 / 1000 / 1100 and AR small / medium / large, which the six numbers above do not restate.  Both come from the flags of the ONE matching: the
-first `c` detections of an image are an evaluation at max_det = c (COCOeval matches once and slices afterwards), and an image's own AP is
-`_sample` on its own list.  `stats_from_flags` states that in numpy and is the checker; on the device ONE cdetr_coco_image_stats launch
-(csrc/coco_report.hip) reads the flags where cdetr_coco_match left them and returns EQUAL numbers, the average precisions bit for bit
+PER-IMAGE STATISTICS (`stats`, infer.py --image_report): the list the reference's evaluator keeps per image (A2/eval_all.py:227-239, its `ap`
+field left empty at line 181) and the counts behind COCOevalMaxDets.summarize's stats[6..11], AR at maxDets 900 / 1000 / 1100 and AR small /
+medium / large.  The first `c` detections of an image are an evaluation at max_det = c (COCOeval matches once and slices afterwards), and an
+image's own AP is `_sample` on its own list.  `stats_from_flags` states that in numpy and is the checker; device flags go through ONE
+cdetr_coco_image_stats launch (csrc/coco_report.hip) where they lie: EQUAL numbers, the average precisions bit for bit
 (tests/test_image_report_cpu.py, _gpu.py).  `average_recall`, `image_rows` and `image_report` turn the statistics into what is
 printed and written.
 """
@@ -53,6 +52,7 @@ IOU_THRS = np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoi
 REC_THRS = np.linspace(0.0, 1.0, int(np.round((1.0 - 0.0) / 0.01)) + 1, endpoint=True)
 AREA_RNG = {"all": (0.0, 1e5 ** 2), "small": (0.0, 32.0 ** 2), "medium": (32.0 ** 2, 96.0 ** 2), "large": (96.0 ** 2, 1e5 ** 2)}
 MAX_DETS = 1100          # A2/eval_all.py:511-512: maxDets = [900, 1000, 1100], AP summarised at the last one
+MAX_DET_CUTS = (900, 1000, 1100)        # COCOeval's maxDets: its AR numbers are read at each, its AP at the last
 
 
 def reference_box(b):
@@ -195,48 +195,123 @@ def _cuda(device):
     return device
 
 
-def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None, keep=None, host=True):
-    """One `cdetr_coco_match` launch for every image of `pack` (from `pack_images`) under the area ranges `areas` ->
-    (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int): `_evaluate_image`'s flags, images side by side.
-    `events`: a pair of torch.cuda.Event recorded around the launch.  A pack that carries "dt_device" = (boxes f64 [D, 4], area f64 [D]) device
-    tensors (`summarize_store`) has its detections read from there; its dt_boxes / dt_area are not used.
-    `keep`: a list that also receives the three device tensors the launch wrote (`_stats_on_device` reads them where they are);
-    `host=False`: only those, no copy (B > 0)."""
-    import torch
-    from . import ops
-    device = _cuda(device)
-    A, T, B, D = len(areas), len(IOU_THRS), len(pack["image_ids"]), len(pack["dt_score"])
-    dt_dev = pack.get("dt_device")
-    if B == 0:
-        return np.zeros((A, T, 0), dtype=bool), np.zeros((A, T, 0), dtype=bool), np.zeros((A, 0), dtype=np.int64)
-    thrs = np.minimum(IOU_THRS, 1 - 1e-10)
-    rng = np.array([AREA_RNG[a] for a in areas], dtype=np.float64).reshape(-1)
-    G = len(pack["gt_area"])
-    dt_host = (pack["dt_boxes"].reshape(-1), pack["dt_area"]) if dt_dev is None else (np.zeros(0), np.zeros(0))
-    f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], dt_host[0], dt_host[1], thrs, rng])
-    i32 = np.concatenate([pack["gt_off"], pack["dt_off"]]).astype(np.int32)
-    with torch.cuda.device(device):
-        f = torch.from_numpy(f64).to(device)
-        i = torch.from_numpy(i32).to(device)
-        ig = torch.from_numpy(pack["gt_ignore"]).to(device)
-        cuts = np.cumsum([0, 4 * G, G, len(dt_host[0]), len(dt_host[1]), T, 2 * A])
-        gt_boxes, gt_area, dt_boxes, dt_area, d_thrs, d_rng = (f[cuts[k]:cuts[k + 1]] for k in range(6))
-        if dt_dev is not None:
-            dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
-        if not host:
-            on_dev = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]), events=events)
-            if keep is not None:
-                keep.extend(on_dev)
-            return on_dev
-        matched, ignored, npig = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]),
-                                                host=True, events=events, keep=keep)
-    return matched, ignored, npig
+class Matching:
+    """The result of ONE matching over one pack: `pack` (`pack_images` / `pack_store`), the area ranges `areas` it was matched under and
+    `_evaluate_image`'s flags, images side by side: matched, det_ignored [A, T, D] and npig [A, B] -- device tensors where the cdetr_coco_match
+    launch left them (`device`: that CUDA device) or numpy arrays from the host matcher (`device` None).  `image_ids`: the images in the
+    caller's own order (a store's), in which prefix lengths `counts` are given; the pack's by default.  Every reading below is of these flags:
+    nothing is matched twice, and the flags come to the host at most once."""
+
+    def __init__(self, pack, areas, matched, det_ignored, npig, image_ids=None):
+        self.pack, self.areas, self.matched, self.det_ignored, self.npig = pack, tuple(areas), matched, det_ignored, npig
+        self.image_ids = pack["image_ids"] if image_ids is None else image_ids
+        self.device = None if isinstance(matched, np.ndarray) else matched.device
+        self._host = (matched, det_ignored, npig) if self.device is None else None
+
+    @classmethod
+    def of(cls, gt_by_img, dt_by_img, device=None, areas=tuple(AREA_RNG), max_det=MAX_DETS):
+        """The dicts of `average_precision` matched by the host matcher (`device` None: `_evaluate_image` per image and area range, the flags
+        concatenated in `pack_images` order) or on a CUDA device (`launch`)."""
+        pack, T = pack_images(gt_by_img, dt_by_img, max_det), len(IOU_THRS)
+        if device is not None:
+            return cls.launch(pack, device, areas)
+        ids = pack["image_ids"]
+        per = [[_evaluate_image(dt_by_img.get(i, []), gt_by_img.get(i, []), AREA_RNG[a], max_det) for i in ids] for a in areas]
+        cat = lambda k: np.stack([np.concatenate([e[k].reshape(T, -1) for e in row] + [np.zeros((T, 0), dtype=bool)], axis=1) for row in per])   # noqa: E731
+        return cls(pack, areas, cat(1), cat(2), np.array([[e[3] for e in row] for row in per], dtype=np.int64).reshape(len(areas), len(ids)))
+
+    @classmethod
+    def launch(cls, pack, device, areas=tuple(AREA_RNG), events=None, image_ids=None):
+        """ONE `cdetr_coco_match` launch for every image of `pack` under the area ranges `areas`; nothing is copied back.  `events`: a pair of
+        torch.cuda.Event recorded around the launch.  A pack that carries "dt_device" = (boxes f64 [D, 4], area f64 [D]) device tensors
+        (`pack_store`) has its detections read from there; its dt_boxes / dt_area are not used.  A pack without an image launches nothing: empty
+        host flags."""
+        import torch
+        from . import ops
+        device = _cuda(device)
+        A, T, B = len(areas), len(IOU_THRS), len(pack["image_ids"])
+        dt_dev = pack.get("dt_device")
+        if B == 0:
+            return cls(pack, areas, np.zeros((A, T, 0), dtype=bool), np.zeros((A, T, 0), dtype=bool), np.zeros((A, 0), dtype=np.int64), image_ids)
+        thrs = np.minimum(IOU_THRS, 1 - 1e-10)
+        rng = np.array([AREA_RNG[a] for a in areas], dtype=np.float64).reshape(-1)
+        G = len(pack["gt_area"])
+        dt_host = (pack["dt_boxes"].reshape(-1), pack["dt_area"]) if dt_dev is None else (np.zeros(0), np.zeros(0))
+        f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], dt_host[0], dt_host[1], thrs, rng])
+        i32 = np.concatenate([pack["gt_off"], pack["dt_off"]]).astype(np.int32)
+        with torch.cuda.device(device):
+            f = torch.from_numpy(f64).to(device)
+            i = torch.from_numpy(i32).to(device)
+            ig = torch.from_numpy(pack["gt_ignore"]).to(device)
+            cuts = np.cumsum([0, 4 * G, G, len(dt_host[0]), len(dt_host[1]), T, 2 * A])
+            gt_boxes, gt_area, dt_boxes, dt_area, d_thrs, d_rng = (f[cuts[k]:cuts[k + 1]] for k in range(6))
+            if dt_dev is not None:
+                dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
+            flags = ops.coco_match(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:], d_thrs, d_rng, int(pack["g_max"]), events=events)
+        return cls(pack, areas, *flags, image_ids)
+
+    def host(self):
+        """-> (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int) on the host: a launch's flags come in ONE copy of its single
+        buffer, taken at the first call and kept."""
+        if self._host is None:
+            from . import ops
+            self._host = ops.coco_flags_host(self.matched, self.det_ignored, self.npig)
+        return self._host
+
+    def precisions(self):
+        """-> precision [T, R] per area range (`accumulate`)."""
+        matched, ignored, npig = self.host()
+        return [accumulate(self.pack["dt_score"], matched[a], ignored[a], int(npig[a].sum())) for a in range(len(self.areas))]
+
+    def six(self):
+        """-> the six numbers of `summarize` (a matching under the four ranges of AREA_RNG)."""
+        return _six(dict(zip(self.areas, self.precisions())))
+
+    def six_sweep(self, thresholds):
+        """-> the six numbers per score threshold (`summarize_flags_sweep`: the detections a threshold keeps are a prefix, checked)."""
+        matched, ignored, npig = self.host()
+        return summarize_flags_sweep(self.pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(self.areas)}, thresholds)
+
+    def pack_counts(self, counts):
+        """Prefix lengths per image of `image_ids` (or None: whole segments) -> per image of the pack, 0 for an image `image_ids` does not name."""
+        if counts is None:
+            return None
+        slot = {int(i): k for k, i in enumerate(self.image_ids)}
+        return [int(counts[slot[i]]) if i in slot else 0 for i in self.pack["image_ids"]]
+
+    def stats(self, cuts=MAX_DET_CUTS, counts=None):
+        """-> the per-image statistics of `image_stats`, of the first counts[k] detections of image k of `image_ids` where `counts` is given.
+        Host flags: `stats_from_flags`.  Device flags: ONE cdetr_coco_image_stats launch on them where they lie and one copy of the statistics
+        back (and the 4 B ints of npig, unless the flags' host copy is there already)."""
+        pack, counts = self.pack, self.pack_counts(counts)
+        if self.device is None:
+            matched, ignored, npig = self._host
+            return _stats_dict(pack["image_ids"], *stats_from_flags(matched, ignored, pack["dt_off"], npig, cuts, counts), npig, cuts)
+        import torch
+        from . import ops
+        npig = self._host[2] if self._host is not None else self.npig.cpu().numpy()
+        B, M = len(pack["image_ids"]), len(cuts)
+        i32 = np.concatenate([pack["dt_off"], np.asarray(cuts, dtype=np.int64), np.asarray([] if counts is None else counts, dtype=np.int64)])
+        with torch.cuda.device(self.device):
+            i = torch.from_numpy(i32.astype(np.int32)).to(self.device)
+            rec = torch.from_numpy(REC_THRS).to(self.device)
+            tp, fp, ap = ops.coco_image_stats(self.matched, self.det_ignored, i[:B + 1], self.npig, i[B + 1:B + 1 + M], rec,
+                                              dt_cnt=None if counts is None else i[B + 1 + M:], host=True)
+        return _stats_dict(pack["image_ids"], tp, fp, ap, npig, cuts)
+
+    def row50(self):
+        """-> (matched, det_ignored) [D] at area range `all`, IoU 0.5, row [0, 0] of the flags, for the renderer: views of the device tensors
+        (no copy), or arrays."""
+        return self.matched[0, 0], self.det_ignored[0, 0]
+
+
+def match_on_device(pack, device, areas=("all", "small", "medium", "large"), events=None):
+    """`Matching.launch` and its flags on the host -> (matched [A, T, D] bool, det_ignored [A, T, D] bool, npig [A, B] int)."""
+    return Matching.launch(pack, device, areas, events).host()
 
 
 def _device_precisions(gt_by_img, dt_by_img, areas, max_det, device):
-    pack = pack_images(gt_by_img, dt_by_img, max_det)
-    matched, ignored, npig = match_on_device(pack, device, areas)
-    return [accumulate(pack["dt_score"], matched[a], ignored[a], int(npig[a].sum())) for a in range(len(areas))]
+    return Matching.of(gt_by_img, dt_by_img, device, areas, max_det).precisions()
 
 
 def average_precision(gt_by_img, dt_by_img, area="all", max_det=MAX_DETS, device=None):
@@ -332,43 +407,27 @@ def pack_store(gt_by_img, store, image_ids):
             "dt_score": np.ascontiguousarray(score), "dt_off": np.concatenate([[0], np.cumsum([n_dt(i) for i in ids])]).astype(np.int32)}
 
 
-def _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept=None):
-    """The shared head of `summarize_store` / `summarize_store_sweep`: the store's pack and the flags of its ONE cdetr_coco_match launch on the
-    host -> (pack, matched, ignored, npig, stats); `report` = (cuts, counts) also runs cdetr_coco_image_stats on the flags where the launch
-    left them (`stats`: the dict of `image_stats`, else None).  counts[k] belongs to the store's image k.  `kept`: a dict that receives what a
-    later reader of the same matching needs (render.py's overlays): "pack", "flags" = the launch's three device tensors (empty without an
-    image), "counts" = `counts` per image of the pack, or None."""
+def match_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS, sweep=None):
+    """The ONE matching of an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections) -> a `Matching` under the four
+    area ranges: the evaluation records go to cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image
+    k (the order of `counts` in `Matching.stats`); `gt_by_img` as for `summarize` (`gt_from_json`); `device`: the store's own (default).
+    `sweep`: the score thresholds a sweep will ask of the matching (`Matching.six_sweep`), refused here, before any device work, unless the
+    store was emitted at the lowest of them."""
+    if sweep is not None:
+        t32 = np.asarray(list(sweep), dtype=np.float64).astype(np.float32)
+        if len(t32) == 0 or np.isnan(t32).any() or np.float32(store.threshold) != t32.min():
+            raise RuntimeError(f"coco_ap: a sweep over {t32.tolist()} needs a store emitted at its lowest threshold, this one was emitted at "
+                               f"{store.threshold}")
     if store.max_det != max_det:
         raise RuntimeError(f"coco_ap: the store was cut at max_det = {store.max_det}, the summary asks for {max_det}")
     device = store.buf.device if device is None else _cuda(device)
-    pack = pack_store(gt_by_img, store, image_ids)
-    keep = [] if report is not None or kept is not None else None
-    matched, ignored, npig = match_on_device(pack, device, tuple(AREA_RNG), keep=keep)
-    stats = None
-    if report is not None:
-        cuts, counts = report
-        if counts is not None:
-            slot = {int(i): k for k, i in enumerate(image_ids)}
-            counts = [int(counts[slot[i]]) if i in slot else 0 for i in pack["image_ids"]]
-        if kept is not None:
-            kept.update(pack=pack, flags=keep, counts=counts)
-        if keep:
-            stats = _stats_on_device(pack, keep, cuts, counts, npig, device)
-        else:                                                              # no image at all: nothing was launched
-            stats = _stats_dict([], *stats_from_flags(matched, ignored, [0], npig, cuts), npig, cuts)
-    return pack, matched, ignored, npig, stats
+    return Matching.launch(pack_store(gt_by_img, store, image_ids), device, image_ids=image_ids)
 
 
-def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS, report=None, kept=None):
-    """`summarize(..., device=)` for an ops.DetectionStore filled by cdetr_emit_detections (infer.py --device_detections): the same six numbers
-    as `ap_from_json(device=)` gives on the predictions json written from that store, without the json trip -- the evaluation records go to
-    cdetr_coco_match straight from device memory.  `image_ids[k]` = the image id of the store's image k; `gt_by_img` as for `summarize`
-    (`gt_from_json`).  `device`: the store's own (default).
-    `report` = (cuts, counts): -> (the six numbers, the per-image statistics of `image_stats_store`) from the SAME matching launch; with it,
-    `kept` (a dict) receives the pack and the device flags of that launch (`_store_flags`)."""
-    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept)
-    by_area = {a: accumulate(pack["dt_score"], matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}
-    return _six(by_area) if report is None else (_six(by_area), stats)
+def summarize_store(gt_by_img, store, image_ids, device=None, max_det=MAX_DETS):
+    """`summarize(..., device=)` for an ops.DetectionStore: the same six numbers as `ap_from_json(device=)` gives on the predictions json written
+    from that store, without the json trip (`match_store`)."""
+    return match_store(gt_by_img, store, image_ids, device, max_det).six()
 
 
 def accumulate_sweep(scores, matched, ignored, npig, thresholds):
@@ -408,25 +467,14 @@ def summarize_flags_sweep(scores, flags, thresholds):
     return [_six({a: per_area[a][k] for a in per_area}) for k in range(len(thresholds))]
 
 
-def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS, report=None, kept=None):
+def summarize_store_sweep(gt_by_img, store, image_ids, thresholds, device=None, max_det=MAX_DETS):
     """`summarize_store` at every score threshold of `thresholds` from ONE cdetr_coco_match launch: the store was emitted at the lowest
     threshold (checked), the flags of every higher one are a prefix of what that launch returns (`accumulate_sweep`).  -> list of the six
-    numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold.
-    `report` = (cuts, counts): -> (that list, the per-image statistics of `image_stats_store`) from the same launch; counts[k] = the
-    detections of the store's image k that the threshold to be reported keeps (a prefix, as above); `kept`: as for `summarize_store`."""
-    t32 = np.asarray(list(thresholds), dtype=np.float64).astype(np.float32)
-    if len(t32) == 0 or np.isnan(t32).any() or np.float32(store.threshold) != t32.min():
-        raise RuntimeError(f"coco_ap: a sweep over {t32.tolist()} needs a store emitted at its lowest threshold, this one was emitted at "
-                           f"{store.threshold}")
-    pack, matched, ignored, npig, stats = _store_flags(gt_by_img, store, image_ids, device, max_det, report, kept)
-    rows = summarize_flags_sweep(pack["dt_score"], {a: (matched[k], ignored[k], int(npig[k].sum())) for k, a in enumerate(AREA_RNG)}, t32)
-    return rows if report is None else (rows, stats)
+    numbers, in the order of `thresholds`; each EQUALS `summarize_store` on a store emitted at that threshold."""
+    return match_store(gt_by_img, store, image_ids, device, max_det, sweep=thresholds).six_sweep(thresholds)
 
 
 # ------------------------------------------------------------------------------------------------- per-image statistics and average recall
-MAX_DET_CUTS = (900, 1000, 1100)        # A2/eval_all.py:511-512: COCOeval's maxDets; its AR numbers are read at each, its AP at the last
-
-
 def stats_from_flags(matched, ignored, dt_off, npig, cuts, counts=None):
     """The definition of cdetr_coco_image_stats in numpy (host only: the checker).  matched / ignored [A, T, D] of ONE matching (images side by
     side, image b owns dt_off[b]:dt_off[b + 1], evaluation order), npig [A, B], `cuts` = maxDets cuts, `counts` [B] = use only the first
@@ -460,47 +508,19 @@ def _stats_dict(ids, tp, fp, ap, npig, cuts):
     return {"image_ids": list(ids), "tp": tp, "fp": fp, "ap": ap, "npig": np.asarray(npig, dtype=np.int64), "cuts": tuple(int(c) for c in cuts)}
 
 
-def _stats_on_device(pack, flags, cuts, counts, npig, device):
-    """cdetr_coco_image_stats on the device tensors `flags` = (matched, det_ignored, npig) of `match_on_device(keep=)`: one launch, one copy
-    back.  `counts`: per image of the pack, or None; `npig`: the host copy the caller already holds."""
-    import torch
-    from . import ops
-    B, M = len(pack["image_ids"]), len(cuts)
-    i32 = np.concatenate([pack["dt_off"], np.asarray(cuts, dtype=np.int64), np.asarray([] if counts is None else counts, dtype=np.int64)])
-    with torch.cuda.device(device):
-        i = torch.from_numpy(i32.astype(np.int32)).to(device)
-        rec = torch.from_numpy(REC_THRS).to(device)
-        tp, fp, ap = ops.coco_image_stats(flags[0], flags[1], i[:B + 1], flags[2], i[B + 1:B + 1 + M], rec,
-                                          dt_cnt=None if counts is None else i[B + 1 + M:], host=True)
-    return _stats_dict(pack["image_ids"], tp, fp, ap, npig, cuts)
-
-
 def image_stats(gt_by_img, dt_by_img, cuts=MAX_DET_CUTS, device=None, max_det=MAX_DETS):
     """Per-image statistics of one evaluation -> {"image_ids" (sorted, images with neither ground truth nor detection left out), "tp", "fp"
     int32 [A, B, T, M], "ap" float64 [A, B, T] (-1: no non-ignored ground truth), "npig" [A, B], "cuts"}; A = the four area ranges of AREA_RNG
     in its order, T = IOU_THRS, M = `cuts`.  device=None: `_evaluate_image`'s flags and `stats_from_flags`, the host path and the checker.  A
     CUDA device: `pack_images`, ONE cdetr_coco_match launch, ONE cdetr_coco_image_stats launch on its flags where they lie, one copy of the
     statistics back (and the 4 B ints of npig) -- EQUAL numbers, `ap` bit for bit."""
-    areas, T = tuple(AREA_RNG), len(IOU_THRS)
-    if device is not None:
-        device = _cuda(device)
-        pack = pack_images(gt_by_img, dt_by_img, max_det)
-        if pack["image_ids"]:
-            flags = match_on_device(pack, device, areas, host=False)
-            return _stats_on_device(pack, flags, cuts, None, flags[2].cpu().numpy(), device)
-    ids = [i for i in sorted(set(gt_by_img) | set(dt_by_img)) if gt_by_img.get(i) or dt_by_img.get(i)]
-    per = [[_evaluate_image(dt_by_img.get(i, []), gt_by_img.get(i, []), AREA_RNG[a], max_det) for i in ids] for a in areas]
-    cat = lambda k: np.stack([np.concatenate([e[k].reshape(T, -1) for e in row] + [np.zeros((T, 0), dtype=bool)], axis=1) for row in per])   # noqa: E731
-    dt_off = np.concatenate([[0], np.cumsum([len(e[0]) for e in per[0]])]).astype(np.int64)
-    npig = np.array([[e[3] for e in row] for row in per], dtype=np.int64).reshape(len(areas), len(ids))
-    return _stats_dict(ids, *stats_from_flags(cat(1), cat(2), dt_off, npig, cuts), npig, cuts)
+    return Matching.of(gt_by_img, dt_by_img, device, max_det=max_det).stats(cuts)
 
 
 def image_stats_store(gt_by_img, store, image_ids, cuts=MAX_DET_CUTS, counts=None):
     """`image_stats(device=)` for an ops.DetectionStore: the detections are read where cdetr_emit_detections left them.  `image_ids[k]` = the id
-    of the store's image k, `counts[k]` = use only its first counts[k] detections (a threshold above the store's own keeps a prefix).
-    `summarize_store(report=(cuts, counts))` gives the six AP numbers from the same matching launch."""
-    return summarize_store(gt_by_img, store, image_ids, report=(cuts, counts))[1]
+    of the store's image k, `counts[k]` = use only its first counts[k] detections (a threshold above the store's own keeps a prefix)."""
+    return match_store(gt_by_img, store, image_ids).stats(cuts, counts)
 
 
 def average_recall(stats):
@@ -574,15 +594,26 @@ def gt_from_json(gt_json, ids):
     return gt_by
 
 
+def dt_from_predictions(pred, ids=None):
+    """{image_id: [detections]} of a predictions dict (the wire format of infer.py / A2/infer.py:84-116) as the matcher sees them: the
+    evaluation boxes (`reference_box`), their areas and scores, of the images `ids` (None: all)."""
+    dt_by = {}
+    for a in pred.get("annotations", []):
+        if ids is None or a["image_id"] in ids:
+            b = reference_box(a["bbox"])
+            dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
+    return dt_by
+
+
+def match_predictions(pred, gt_json, image_ids, device=None, areas=tuple(AREA_RNG)):
+    """The ONE matching of a predictions dict as written against the ground truth `gt_json` holds for `image_ids` -> a `Matching` (`device` None:
+    the host matcher)."""
+    return Matching.of(gt_from_json(gt_json, image_ids), dt_from_predictions(pred), device, areas)
+
+
 def ap_from_json(pred_json, gt_json, image_ids=None, device=None):
-    """AP of `predictions_<split>.json` (the wire format of infer.py / A2/infer.py:84-116) against `instances_<split>.json`.
-    `device`: passed to `summarize`."""
+    """AP of `predictions_<split>.json` against `instances_<split>.json`.  `device`: passed to `summarize`."""
     with open(pred_json) as f:
         pred = json.load(f)
     ids = set(image_ids) if image_ids is not None else {im["id"] for im in pred.get("images", [])} or {a["image_id"] for a in pred["annotations"]}
-    gt_by, dt_by = gt_from_json(gt_json, ids), {}
-    for a in pred.get("annotations", []):
-        if a["image_id"] in ids:
-            b = reference_box(a["bbox"])
-            dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
-    return summarize(gt_by, dt_by, device=device)
+    return summarize(gt_from_json(gt_json, ids), dt_from_predictions(pred, ids), device=device)

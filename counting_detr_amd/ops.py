@@ -2020,13 +2020,12 @@ def box_iou_xywh(dt, gt):
     return iou
 
 
-def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, iou_thrs, area_rng, g_max, host=False, events=None, keep=None):
+def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, iou_thrs, area_rng, g_max, events=None):
     """cdetr_coco_match: COCOeval's greedy matcher for B packed images x A area ranges x T IoU thresholds in one launch (device tensors:
     float64 boxes [*, 4] / areas / thresholds [T] / ranges [A, 2], uint8 ignore flags, int32 offset tables [B + 1]; detections in evaluation
     order; g_max = the largest ground-truth count of one image, known on the host).  -> matched [A, T, D], det_ignored [A, T, D] (uint8),
-    npig [A, B] (int32): views of ONE byte buffer; host=True returns them as numpy arrays (bool, bool, int32) after a single copy.
-    events: a pair of torch.cuda.Event recorded right before / after the launch (tools/coco_ap_time.py).
-    keep: a list that receives the three device views as well when host=True (coco_image_stats reads them without a host trip)."""
+    npig [A, B] (int32): device views of ONE byte buffer, which is the `_base` of each of them; `coco_flags_host` brings the three to the
+    host in a single copy of it.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/coco_ap_time.py)."""
     from ._ffi import CocoMatchDesc
     dev = gt_off.device
     B, T, A = gt_off.numel() - 1, iou_thrs.numel(), area_rng.numel() // 2
@@ -2047,19 +2046,24 @@ def coco_match(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, 
     d.matched, d.det_ignored, d.npig = buf.data_ptr(), buf.data_ptr() + n_flag, buf.data_ptr() + n_pad
     with _between(events):
         check(lib().cdetr_coco_match(C.byref(d), stream_ptr()), "cdetr_coco_match")
-    views = buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
-    if host:
-        if keep is not None:
-            keep.extend(views)
-        h = buf.cpu().numpy()
-        return (h[:n_flag].reshape(A, T, D).astype(bool), h[n_flag:2 * n_flag].reshape(A, T, D).astype(bool),
-                h[n_pad:].view("int32").reshape(A, B))
-    return views
+    return buf[:n_flag].view(A, T, D), buf[n_flag:2 * n_flag].view(A, T, D), buf[n_pad:].view(torch.int32).view(A, B)
+
+
+def coco_flags_host(matched, det_ignored, npig):
+    """The three views coco_match returned -> numpy arrays (bool [A, T, D], bool [A, T, D], int32 [A, B]) after ONE copy of the buffer they
+    share: the flags at its head, npig at its end."""
+    (A, T, D), B, buf = matched.shape, npig.shape[1], matched._base
+    n_flag = A * T * D
+    if buf is None or det_ignored.shape != matched.shape or npig.data_ptr() != buf.data_ptr() + buf.numel() - 4 * A * B:
+        raise RuntimeError("coco_flags_host: the three tensors are not the views one coco_match call returned")
+    h = buf.cpu().numpy()
+    return (h[:n_flag].reshape(A, T, D).astype(bool), h[n_flag:2 * n_flag].reshape(A, T, D).astype(bool),
+            h[h.size - 4 * A * B:].view("int32").reshape(A, B))
 
 
 def coco_image_stats(matched, det_ignored, dt_off, npig, cuts, rec_thrs, dt_cnt=None, host=False, events=None):
     """cdetr_coco_image_stats: per (area range, image, IoU threshold) the true / false positives at every maxDets cut and the image's own
-    average precision, from the flags of coco_match(host=False) as they lie in device memory (device tensors: uint8 matched / det_ignored
+    average precision, from the flags of coco_match as they lie in device memory (device tensors: uint8 matched / det_ignored
     [A, T, D], int32 dt_off [B + 1], npig [A, B], cuts [M], dt_cnt [B] or None = whole segments; float64 rec_thrs [R]).
     -> tp [A, B, T, M], fp [A, B, T, M] (int32), ap [A, B, T] (float64): views of ONE byte buffer; host=True returns them as numpy arrays
     after a single copy.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/image_report_time.py)."""

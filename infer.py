@@ -33,7 +33,7 @@ field its line 181 left empty, and COCOeval's six recall numbers beside the six 
 and image_report_<split>.json appears beside the predictions file ({"split", "threshold", "max_dets", "AR", "rows", "order_by_ap",
 "order_by_diff"}; a row = image_id, count_gt, count_pred, diff, the image's own AP / AP50 / AP75 / APs / APm / APl, tp50 / fp50 / fn50).  On the
 device path the flags of the split's one matching go through ONE cdetr_coco_image_stats launch where they lie; every other run forms the
-same numbers from the written predictions (coco_ap.image_stats; `--ap_on_host`: its host code, the checker).  With --sweep_thresholds the
+same numbers from one matching of the written predictions (coco_ap.match_predictions; `--ap_on_host`: its host code, the checker).  With --sweep_thresholds the
 report describes the run's own --threshold.  Without the flag nothing changes.
 
 `--render_worst K` / `--render_ids 3,17` (both need --image_report; an error at start-up otherwise) SHOW those images -- the step the reference's
@@ -63,7 +63,7 @@ import torch
 import counting_detr_amd
 from counting_detr_amd import data
 from counting_detr_amd.args import get_args_parser
-from counting_detr_amd.coco_ap import gt_from_json, reference_box, summarize_sweep
+from counting_detr_amd.coco_ap import MAX_DET_CUTS, MAX_DETS, gt_from_json, match_predictions, match_store, reference_box, summarize_sweep
 from counting_detr_amd.engine import count_from_logits, counting_metrics
 from counting_detr_amd.misc import NestedTensor
 
@@ -75,31 +75,21 @@ class ImageReport:
     def __init__(self, gt_json, device=None):
         self.gt_json, self.device, self.split, self.report = gt_json, device, None, None
 
-    def fill(self, stats, image_ids, gt_counts, pred_counts, threshold):
+    def from_matching(self, matching, counts, image_ids, gt_counts, pred_counts, threshold):
+        """The report of the images `image_ids` (in the order they were run) from the statistics of ONE coco_ap.Matching -> its AR numbers.
+        `counts`: the prefix lengths of `Matching.stats` (None: every detection the matching saw)."""
         from counting_detr_amd.coco_ap import image_report
-        self.report = image_report(stats, image_ids, gt_counts, pred_counts, self.split, threshold)
+        self.report = image_report(matching.stats(MAX_DET_CUTS, counts), image_ids, gt_counts, pred_counts, self.split, threshold)
         return self.report["AR"]
 
     def from_predictions(self, predictions, image_ids, gt_counts, pred_counts, threshold):
-        """The route of every pass whose detections are not matched from the device store: coco_ap.image_stats on the annotations of the
-        predictions file as written (`ap_from_json`'s reading of them)."""
-        from counting_detr_amd.coco_ap import image_stats
-        dt_by = _detections_as_written(predictions)
-        return self.fill(image_stats(gt_from_json(self.gt_json, image_ids), dt_by, device=self.device), image_ids, gt_counts, pred_counts, threshold)
+        """`from_matching` for a predictions dict as written (`coco_ap.match_predictions`), matched where `device` says."""
+        return self.from_matching(match_predictions(predictions, self.gt_json, image_ids, self.device), None, image_ids, gt_counts, pred_counts, threshold)
 
     def write(self, output_dir):
         if self.report is not None:
             with open(os.path.join(output_dir, "image_report_" + self.split + ".json"), "w") as handle:
                 json.dump(self.report, handle)
-
-
-def _detections_as_written(predictions):
-    """{image_id: [detections]} of a predictions dict, as `coco_ap.ap_from_json` reads the file: the evaluation boxes the matcher sees."""
-    dt_by = {}
-    for a in predictions["annotations"]:
-        b = reference_box(a["bbox"])
-        dt_by.setdefault(a["image_id"], []).append({"bbox": b, "score": float(a["score"]), "area": float(b[2] * b[3])})
-    return dt_by
 
 
 class Render:
@@ -111,41 +101,22 @@ class Render:
         self.data_path, self.worst, self.ids, self.out_dir = data_path, int(worst), tuple(ids), None
 
     def from_predictions(self, predictions, image_ids, image_report, output_dir, threshold):
-        """The route of every pass whose detections are not matched from the device store: the predictions as written are packed and
-        matched again at area range `all` -- `image_report.device` None (--ap_on_host): coco_ap's host matcher and render.py's host
-        implementation, the checker; a CUDA device: one cdetr_coco_match launch whose flags stay there, one cdetr_render_boxes launch."""
-        import numpy as np
-        from counting_detr_amd import coco_ap as ca
-        gt_by, dt_by = gt_from_json(image_report.gt_json, image_ids), _detections_as_written(predictions)
-        pack = ca.pack_images(gt_by, dt_by)
-        device, T = image_report.device, len(ca.IOU_THRS)
-        if device is None:
-            per = [ca._evaluate_image(dt_by.get(i, []), gt_by.get(i, []), ca.AREA_RNG["all"], ca.MAX_DETS) for i in pack["image_ids"]]
-            matched50 = np.concatenate([e[1].reshape(T, -1)[0] for e in per] + [np.zeros(0, dtype=bool)])
-            ignored50 = np.concatenate([e[2].reshape(T, -1)[0] for e in per] + [np.zeros(0, dtype=bool)])
-        else:
-            flags = []
-            ca.match_on_device(pack, device, ("all",), keep=flags, host=False)
-            matched50, ignored50 = (flags[0][0, 0], flags[1][0, 0]) if flags else (np.zeros(0, dtype=bool), np.zeros(0, dtype=bool))
-        return self.draw(pack, matched50, ignored50, None, device, image_report, output_dir, threshold)
+        """`from_matching` for a predictions dict as written, matched at area range `all` where `image_report.device` says."""
+        matching = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device, ("all",))
+        return self.from_matching(matching, None, image_report, output_dir, threshold)
 
-    def from_store(self, kept, device, image_report, output_dir, threshold):
-        """The route of --device_detections: `kept` = what the store's ONE matching left (coco_ap.summarize_store(kept=)): the boxes are read
-        from pack["dt_device"], the flags from the launch's tensors, the prefix lengths are the counts at the run's threshold."""
-        import numpy as np
-        flags = kept["flags"]
-        matched50, ignored50 = (flags[0][0, 0], flags[1][0, 0]) if flags else (np.zeros(0, dtype=bool), np.zeros(0, dtype=bool))
-        return self.draw(kept["pack"], matched50, ignored50, kept["counts"], device, image_report, output_dir, threshold)
-
-    def draw(self, pack, matched50, ignored50, dt_cnt, device, image_report, output_dir, threshold):
+    def from_matching(self, matching, counts, image_report, output_dir, threshold):
+        """The overlays from what ONE coco_ap.Matching holds: the pack's boxes (a store's are read on its device), row [0, 0] of the flags where
+        they lie and the prefix lengths `counts` (as for `ImageReport.from_matching`).  Host flags (--ap_on_host) are drawn by render.py's
+        host implementation, the checker; device flags by one cdetr_render_boxes launch there."""
         from counting_detr_amd import render as rd
-        report = image_report.report
+        pack, report = matching.pack, image_report.report
         picks = rd.select(report, self.worst, self.ids)
         canvases, files, exemplars = rd.load_canvases(self.data_path, image_report.split, [p["image_id"] for p in picks])
         at = {i: b for b, i in enumerate(pack["image_ids"])}
         drawn = [k for k, p in enumerate(picks) if p["image_id"] in at]             # an image with neither ground truth nor detection is not packed
-        overlays = rd.render_images([canvases[k] for k in drawn], pack, matched50, ignored50, [at[picks[k]["image_id"]] for k in drawn], dt_cnt=dt_cnt,
-                                    exemplars=[exemplars[k] for k in drawn], device=device) if drawn else []
+        overlays = rd.render_images([canvases[k] for k in drawn], pack, *matching.row50(), [at[picks[k]["image_id"]] for k in drawn],
+                                    dt_cnt=matching.pack_counts(counts), exemplars=[exemplars[k] for k in drawn], device=matching.device) if drawn else []
         by_pick = dict(zip(drawn, overlays))
         overlays = [by_pick[k] if k in by_pick else rd.paint_first_hit(canvases[k], *rd.primitives([], [], [], exemplars[k]))       # exemplars only
                     for k in range(len(picks))]
@@ -278,11 +249,12 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows)
     _write_sweep(sweep, output_dir, split)
     if image_report is not None and n_img:
-        metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
+        matching = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device)       # once, for the report and the overlays
+        metrics.update(image_report.from_matching(matching, None, image_ids, gt_counts, pred_counts, threshold))
         if output_path is not None:
             image_report.write(output_dir)
             if render is not None:
-                render.from_predictions(predictions, image_ids, image_report, output_dir, threshold)
+                render.from_matching(matching, None, image_report, output_dir, threshold)
     return metrics, predictions
 
 
@@ -310,19 +282,17 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
     and image ids into a device table.  After the loop: one copy each of the store, the table and the loss buffer; the json is written from the
     store's arrays (same bytes as the host loop's file), the losses are summed in Python in the same order (same floats), the counts are the
-    store's, and the AP (`gt_json`) is coco_ap.summarize_store on the store -- the file is not read back.
+    store's.  Everything that needs the box ground truth then reads ONE coco_ap.Matching of the store (`match_store`; the file is not read
+    back): the six AP numbers (`gt_json`), the report's statistics and the overlays.
     `sweep`: the store is emitted at the sweep's LOWEST threshold and one cdetr_count_sweep call per batch (ops.ThresholdSweep) sits beside the
     emit; after the loop one more copy brings the [N, T] table.  The file takes the wire records with score >= `threshold` (query order, ids
-    from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, and the AP of every threshold comes
-    from ONE matching (coco_ap.summarize_store_sweep), the returned six numbers being its row at `threshold`.
-    `image_report` with `gt_json`: that one matching's flags also go through cdetr_coco_image_stats where they lie (with a sweep: the prefix
-    of every image that `threshold` keeps, min(its count there, max_det)); without `gt_json` the report is formed from the predictions dict.
-    `render` (with `output_path`): the overlays are drawn from what that matching left on the device -- the store's boxes, the flags, those
-    prefix lengths --, only the chosen images' pixels go up and only the overlays come back; without `gt_json`: from the predictions dict."""
+    from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, the AP of every threshold is a
+    reading of that matching (`six_sweep`), the returned six numbers being its row at `threshold`, and the report and the overlays take the
+    prefix of every image that `threshold` keeps, min(its count there, max_det).
+    Without `gt_json` the report and the overlays are formed from the predictions dict as written (`match_predictions`, once for both)."""
     import numpy as np
     from counting_detr_amd import ops
     from counting_detr_amd import threshold_sweep as ts
-    from counting_detr_amd.coco_ap import MAX_DET_CUTS, MAX_DETS, summarize_store, summarize_store_sweep
     if device.type != "cuda":
         raise RuntimeError(f"infer: device_detections runs HIP kernels, device={device} has none (the default is the host path)")
     N = _num_images(data_loader)
@@ -396,37 +366,24 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
         if n_img:
             metrics.update(counting_metrics(pred_counts, gt_counts))
         metrics["images"] = n_img
-        from_store = image_report is not None and gt_json is not None         # the statistics ride on the store's one matching
-        stats = None
-        kept = {} if render is not None and from_store and output_path is not None else None
+        ap_json = sweep.gt_json if sweep is not None and sweep.gt_json is not None else gt_json
+        matching = counts = ap_rows = None
+        if ap_json is not None and n_img:                   # the store's ONE matching: everything below reads it
+            matching = match_store(gt_from_json(ap_json, image_ids), store, image_ids, sweep=sweep.thresholds if sweep is not None else None)
         if sweep is not None and n_img:
-            ap_json, ap_rows = sweep.gt_json if sweep.gt_json is not None else gt_json, None
-            if ap_json is not None:
-                if from_store:
-                    at_threshold = np.minimum(sweep.counts[:, col], MAX_DETS)
-                    ap_rows, stats = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds,
-                                                           report=(MAX_DET_CUTS, at_threshold), kept=kept)
-                else:
-                    ap_rows = summarize_store_sweep(gt_from_json(ap_json, image_ids), store, image_ids, sweep.thresholds)
-                if gt_json is not None:
-                    metrics.update(ap_rows[col])
+            if matching is not None:                        # the report and the overlays describe `threshold`: a prefix of every image of the store
+                ap_rows, counts = matching.six_sweep(sweep.thresholds), np.minimum(sweep.counts[:, col], MAX_DETS)
             sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
-        elif from_store and n_img:
-            six, stats = summarize_store(gt_from_json(gt_json, image_ids), store, image_ids, report=(MAX_DET_CUTS, None), kept=kept)
-            metrics.update(six)
-        elif gt_json is not None and n_img:
-            metrics.update(summarize_store(gt_from_json(gt_json, image_ids), store, image_ids))
-        if stats is not None:
-            metrics.update(image_report.fill(stats, image_ids, gt_counts, pred_counts, threshold))
-        elif image_report is not None and n_img:
-            if predictions is None:
-                raise RuntimeError("infer: an image report without the device matching (gt_json) is formed from the predictions file: write_json=False")
-            metrics.update(image_report.from_predictions(predictions, image_ids, gt_counts, pred_counts, threshold))
-        if render is not None and output_path is not None and image_report.report is not None:
-            if kept:
-                render.from_store(kept, device, image_report, output_dir, threshold)
-            else:
-                render.from_predictions(predictions, image_ids, image_report, output_dir, threshold)
+        if matching is not None and gt_json is not None:
+            metrics.update(matching.six() if ap_rows is None else ap_rows[col])
+        if image_report is not None and n_img:
+            if gt_json is None:                             # no device matching asked for: the report is formed from the predictions as written
+                if predictions is None:
+                    raise RuntimeError("infer: an image report without the device matching (gt_json) is formed from the predictions file: write_json=False")
+                matching, counts = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device), None
+            metrics.update(image_report.from_matching(matching, counts, image_ids, gt_counts, pred_counts, threshold))
+            if render is not None and output_path is not None:
+                render.from_matching(matching, counts, image_report, output_dir, threshold)
     return metrics, predictions
 
 

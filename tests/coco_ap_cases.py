@@ -109,3 +109,24 @@ def assert_tie_bars(st):
     for area in ("small", "medium", "large"):
         assert st[area]["matched_ignored"] > 0 and st[area]["unmatched_ignored"] > 0, (area, st)
     assert st["all"]["first_differs_from_last"], st
+
+
+def matching_sets():
+    """Small members of the two families for the readings of one coco_ap.Matching, each with an image of ground truths only and one of
+    detections only (and one with neither in `tie`), and the empty set."""
+    tie = tie_family(seed=3, shapes=((20, 60), (0, 7), (9, 0), (12, 30)))
+    tie[0][99], tie[1][99] = [], []
+    return {"tie": tie, "float": float_family(seed=5, shapes=((15, 40), (6, 0), (0, 12))), "empty": ({}, {})}
+
+
+def same_six(a, b):
+    assert list(a) == list(b) and all(a[k] == b[k] or (np.isnan(a[k]) and np.isnan(b[k])) for k in a), (a, b)
+
+
+def same_stats(a, b):
+    """Two dicts of coco_ap.image_stats, field by field; the average precisions as float64 bits."""
+    assert a["image_ids"] == b["image_ids"] and a["cuts"] == b["cuts"] and np.array_equal(a["npig"], b["npig"])
+    for k in ("tp", "fp", "ap"):
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, k
+    assert np.array_equal(a["tp"], b["tp"]) and np.array_equal(a["fp"], b["fp"])
+    assert np.array_equal(np.ascontiguousarray(a["ap"]).view(np.int64), np.ascontiguousarray(b["ap"]).view(np.int64))

@@ -195,6 +195,46 @@ def test_summary_numbers_are_equal_end_to_end(tmp_path):
     assert _same(ca.ap_from_json(str(pj), str(gj), image_ids=ids), ca.ap_from_json(str(pj), str(gj), image_ids=ids, device=DEV))
 
 
+@pytest.mark.parametrize("name", ["tie", "float"])
+def test_one_device_matching_answers_everything_as_the_host_matching_does(name):
+    """ONE coco_ap.Matching on the device, asked for the six numbers, the sweep, the statistics (with prefix lengths), row [0, 0] and the six
+    again: one cdetr_coco_match launch, one cdetr_coco_image_stats launch, two Tensor.cpu calls (the launch's buffer once, the statistics) and
+    none when everything but the statistics is asked again; every answer equals the host matching's (tests/test_matching_cpu.py)."""
+    from counting_detr_amd import ops
+    gts, dts = cc.matching_sets()[name]
+    thresholds, cuts = (0.0, 0.25, 0.5, 0.9, 2.0), (5, 20, 1100)
+    host = ca.Matching.of(gts, dts)
+    counts = [0, 1000] + [n // 2 for n in np.diff(host.pack["dt_off"]).tolist()[2:]]
+    calls = {"coco_match": 0, "coco_image_stats": 0, "cpu": 0}
+    real = {"coco_match": ops.coco_match, "coco_image_stats": ops.coco_image_stats, "cpu": torch.Tensor.cpu}
+
+    def counted(fn):
+        def call(*a, **kw):
+            calls[fn] += 1
+            return real[fn](*a, **kw)
+        return call
+    try:
+        ops.coco_match, ops.coco_image_stats, torch.Tensor.cpu = counted("coco_match"), counted("coco_image_stats"), counted("cpu")
+        m = ca.Matching.of(gts, dts, device=DEV)
+        assert calls == {"coco_match": 1, "coco_image_stats": 0, "cpu": 0}                       # nothing is copied back at construction
+        six, rows, stats, row, again = m.six(), m.six_sweep(thresholds), m.stats(cuts, counts), m.row50(), m.six()
+        assert calls == {"coco_match": 1, "coco_image_stats": 1, "cpu": 2}
+        second = m.six(), m.six_sweep(thresholds), m.row50(), m.host()
+        assert calls == {"coco_match": 1, "coco_image_stats": 1, "cpu": 2}
+    finally:
+        ops.coco_match, ops.coco_image_stats, torch.Tensor.cpu = real["coco_match"], real["coco_image_stats"], real["cpu"]
+    assert m.device == torch.device(DEV) and m.matched.is_cuda and m.pack["image_ids"] == host.pack["image_ids"] and m.areas == host.areas
+    cc.same_six(six, host.six()); cc.same_six(again, six); cc.same_six(second[0], six)
+    for got, want in zip(rows + second[1], host.six_sweep(thresholds) * 2):
+        cc.same_six(got, want)
+    cc.same_stats(stats, host.stats(cuts, counts))
+    assert row[0].is_cuda and row[0].data_ptr() == m.matched.data_ptr() and row[1].data_ptr() == m.det_ignored.data_ptr()      # views: no copy
+    for got, want in zip(row, host.row50()):
+        assert np.array_equal(got.cpu().numpy().astype(bool), want)
+    for got, want in zip(second[3], host.host()):
+        assert got.shape == want.shape and np.array_equal(got, want)
+
+
 def test_launches_are_stream_ordered_and_leave_no_state():
     a = cc.tie_family(seed=6, shapes=((150, 200), (10, 30)))
     b = cc.float_family(seed=7, shapes=((20, 15), (300, 500), (64, 64)))

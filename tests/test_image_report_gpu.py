@@ -193,7 +193,8 @@ def test_device_route_and_store_route_equal_the_host_route():
     assert want["image_ids"] == [3, 7, 11, 20] and (want["ap"][0] > 0).any() and (want["ap"][0, :3] < 1).all()
     stats_same(ca.image_stats(gt_by, dt_by, device=DEV), want)
     stats_same(ca.image_stats_store(gt_by, store, image_ids), want)
-    six, stats = ca.summarize_store(gt_by, store, image_ids, report=(ca.MAX_DET_CUTS, None))
+    matching = ca.match_store(gt_by, store, image_ids)                                       # the reporting matching: the six numbers and the statistics
+    six, stats = matching.six(), matching.stats(ca.MAX_DET_CUTS)
     plain = ca.summarize_store(gt_by, store, image_ids)
     assert set(six) == set(plain) and all(six[k] == plain[k] or (np.isnan(six[k]) and np.isnan(plain[k])) for k in plain)
     stats_same(stats, want)

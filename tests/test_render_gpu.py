@@ -129,9 +129,9 @@ def test_one_crowded_image():
 def test_flags_where_the_matching_left_them():
     gts, dts = cc.float_family()
     pack = ca.pack_images(gts, dts)
-    keep = []
-    on_dev = ca.match_on_device(pack, DEV, keep=keep, host=False)
-    assert len(keep) == 3 and keep[0] is on_dev[0] and keep[0].is_cuda and keep[0].shape[:2] == (4, 10)
+    matching = ca.Matching.launch(pack, DEV)
+    keep = [matching.matched, matching.det_ignored, matching.npig]
+    assert all(k.is_cuda for k in keep) and keep[0].shape == keep[1].shape == (4, 10, len(pack["dt_score"])) and matching.device == keep[0].device
     rng = np.random.default_rng(16)
     B = len(pack["image_ids"])
     canvases = [rng.integers(0, 256, (300 + 17 * k, 420 - 31 * k, 3), dtype=np.uint8) for k in range(B)]
@@ -140,8 +140,9 @@ def test_flags_where_the_matching_left_them():
     assert sum(has(w, rr.TP) for w in want) >= 2 and sum(has(w, rr.FP) for w in want) >= 2
     ex = [np.zeros((0, 4))] * B
     with torch.cuda.device(DEV):
-        kwargs, pix_off = render.device_inputs(canvases, pack, keep[0][0, 0], keep[1][0, 0], list(range(B)), None, ex, render.DEFAULT_STYLE, 1, DEV)
+        kwargs, pix_off = render.device_inputs(canvases, pack, *matching.row50(), list(range(B)), None, ex, render.DEFAULT_STYLE, 1, DEV)
         assert kwargs["matched50"].data_ptr() == keep[0].data_ptr() and kwargs["ignored50"].data_ptr() == keep[1].data_ptr()      # no copy of the flags
+        assert keep[0].data_ptr() == keep[0]._base.data_ptr() and keep[1]._base.data_ptr() == keep[0].data_ptr()                  # the launch's one buffer
         host = ops.render_boxes(**kwargs).cpu().numpy()
     same_images([host[pix_off[k]:pix_off[k + 1]].reshape(canvases[k].shape) for k in range(B)], want)
 

@@ -82,9 +82,9 @@ def main():
     for name, (gts, dts) in sets:
         pack = ca.pack_images(gts, dts)
         B = len(pack["image_ids"])
-        keep = []
         with torch.cuda.device(dev):
-            matched, ignored, npig = ca.match_on_device(pack, dev, areas, keep=keep)
+            matching = ca.Matching.launch(pack, dev, areas)
+            keep, (matched, ignored, npig) = (matching.matched, matching.det_ignored, matching.npig), matching.host()
             dt_off = torch.from_numpy(pack["dt_off"]).to(dev)
             d_cuts, rec = torch.tensor(cuts, dtype=torch.int32, device=dev), torch.from_numpy(ca.REC_THRS).to(dev)
             ops.coco_image_stats(keep[0], keep[1], dt_off, keep[2], d_cuts, rec)                      # warm-up
