@@ -104,10 +104,23 @@ class EmitPseudoLabelsDesc(C.Structure):
                 ("eval_score", _p), ("status", _p)]
 
 
+# cdetr_nms_suppress_desc, field for field; `nms_suppress_desc()` makes one (the twin class is built on first use and kept)
+NMS_SUPPRESS_FIELDS = [("B", C.c_int32), ("Q", C.c_int32), ("threshold", C.c_float), ("pad_", C.c_int32), ("iou", C.c_double),
+                       ("prob", _p), ("boxes", _p), ("orig_hw", _p), ("prob_out", _p), ("removed", _p)]
+_desc_types = {}
+
+
+def nms_suppress_desc():
+    """A zeroed cdetr_nms_suppress_desc."""
+    if "nms" not in _desc_types:
+        _desc_types["nms"] = type("NmsSuppressDesc", (C.Structure,), {"_fields_": NMS_SUPPRESS_FIELDS})
+    return _desc_types["nms"]()
+
+
 EXPORTS = ["cdetr_gemm", "cdetr_gemm_dl", "cdetr_gemm_group", "cdetr_wgrad", "cdetr_wgrad_group", "cdetr_colsum", "cdetr_sumsq", "cdetr_adamw_step", "cdetr_adamw_step2", "cdetr_sgd_step", "cdetr_relu_mask", "cdetr_relu_mask2", "cdetr_layernorm_fwd", "cdetr_layernorm_fwd_add", "cdetr_layernorm_bwd", "cdetr_layernorm_bwd_merge", "cdetr_groupnorm_fwd", "cdetr_groupnorm_bwd", "cdetr_groupnorm_fwd_ws", "cdetr_groupnorm_bwd_ws", "cdetr_posadd2",
            "cdetr_hw_reduce", "cdetr_posadd2_hw_reduce", "cdetr_bcast_add2", "cdetr_bcast_add2_sum", "cdetr_add2", "cdetr_grad_merge", "cdetr_sine_embed", "cdetr_sine_embed_bwd", "cdetr_maxpool3x3s2", "cdetr_maxpool3x3s2_split", "cdetr_weight_mirror", "cdetr_weight_images", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_mha_fwd", "cdetr_mha_bwd", "cdetr_mha_fwd_lens", "cdetr_mha_bwd_lens", "cdetr_attn_fwd", "cdetr_attn_bwd",
            "cdetr_mask_prep", "cdetr_stem_pack", "cdetr_exemplar_fwd", "cdetr_exemplar_bwd", "cdetr_aggr_weight_fwd", "cdetr_aggr_weight_bwd",
-           "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_criterion_eval", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_bbox_criterion_lens_fwd", "cdetr_bbox_criterion_lens_bwd", "cdetr_box_iou_xywh", "cdetr_coco_match", "cdetr_coco_image_stats", "cdetr_render_boxes", "cdetr_image_prep", "cdetr_emit_detections", "cdetr_emit_pseudo_labels", "cdetr_count_sweep", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
+           "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_criterion_eval", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_bbox_criterion_lens_fwd", "cdetr_bbox_criterion_lens_bwd", "cdetr_box_iou_xywh", "cdetr_coco_match", "cdetr_coco_image_stats", "cdetr_render_boxes", "cdetr_image_prep", "cdetr_emit_detections", "cdetr_emit_pseudo_labels", "cdetr_count_sweep", "cdetr_nms_suppress", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
 
 _lib = None
 
@@ -245,6 +258,8 @@ def lib():
         L.cdetr_emit_pseudo_labels.argtypes = [_p, _p]
         L.cdetr_count_sweep.restype = C.c_int
         L.cdetr_count_sweep.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, _p, C.c_int32, C.c_int32, _p]
+        L.cdetr_nms_suppress.restype = C.c_int
+        L.cdetr_nms_suppress.argtypes = [_p, _p]
         if L.cdetr_abi_version() != 2:
             raise RuntimeError("libcdetr_hip.so ABI version mismatch")
         _lib = L

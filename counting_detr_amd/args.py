@@ -133,6 +133,13 @@ def get_args_parser():
                         "a CUDA device one cdetr_render_boxes launch; --ap_on_host: the host painter, the same bytes")
     p.add_argument("--render_ids", default=argparse.SUPPRESS, type=_id_list, metavar="ID,ID",
                    help="with --image_report: also draw the images with these ids (a comma list); usable without --render_worst")
+    # like the flags above: no attribute when it is not given
+    p.add_argument("--nms_iou", default=argparse.SUPPRESS, type=_nms_iou, metavar="T",
+                   help="infer.py / main.py --eval / --eval_every: greedy suppression of duplicate detections ahead of everything that reads the "
+                        "probabilities -- walking each image's queries by descending score, one whose box overlaps an earlier SURVIVING one with "
+                        "IoU > T is dropped (counting_detr_amd/nms.py states the rule).  T in [0, 1]; 1 suppresses nothing.  Works with --threshold, "
+                        "--sweep_thresholds, --image_report and --render_worst; the metrics gain nms_removed.  With --device_detections: one "
+                        "cdetr_nms_suppress launch per batch")
     return p
 
 
@@ -163,6 +170,15 @@ def check_render_flags(ns, fail=None):
 def _id_list(text):
     """--render_ids: `3,17` -> [3, 17]."""
     return [int(t) for t in text.split(",") if t.strip()]
+
+
+def _nms_iou(text):
+    """--nms_iou: a finite number in [0, 1] (argparse turns the ValueError into a usage error)."""
+    from .nms import check_iou
+    try:
+        return check_iou(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def _threshold(text):

@@ -51,15 +51,6 @@ __device__ __forceinline__ wire_fields wire_of(const float* __restrict__ box, co
     return r;
 }
 
-// ascending key = descending score, equal scores by ascending query: high half = the inverted image of the score under the
-// order-preserving map float -> uint32 (sign bit flipped for positives, all bits for negatives; -0 is made +0 first, the two compare equal)
-__device__ __forceinline__ unsigned long long sort_key(float p, int q) {
-    if (p == 0.0f) p = 0.0f;
-    unsigned u = __float_as_uint(p);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)(~u) << 32) | (unsigned)q;
-}
-
 // One workgroup = one image of the batch.
 __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detections_desc p) {
     __shared__ unsigned long long key[EMIT_MAX_Q];
@@ -114,23 +105,8 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_kernel(cdetr_emit_detection
     }
     if (ecnt == 0) return;
 
-    // stable order by (score descending, query ascending): bitonic sort of the padded keys in LDS
-    int npad = 1;
-    while (npad < cnt) npad <<= 1;
-    for (int i = cnt + threadIdx.x; i < npad; i += EMIT_THREADS) key[i] = ~0ull;
-    __syncthreads();
-    for (int k2 = 2; k2 <= npad; k2 <<= 1) {
-        for (int j = k2 >> 1; j >= 1; j >>= 1) {
-            for (int i = threadIdx.x; i < npad; i += EMIT_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = key[i], c = key[l];
-                    if ((a > c) == ((i & k2) == 0)) { key[i] = c; key[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // stable order by (score descending, query ascending): bitonic sort of the padded keys in LDS (records.h)
+    sort_keys<EMIT_THREADS>(key, cnt);
 
     // evaluation records: coco_ap.reference_box on the wire integers ([int(cx - w/2), int(cy - h/2), w, h] = tdiv2(2 cx - w), ...: C++'s
     // integer division truncates toward zero like int()), area = w * h, score, as float64

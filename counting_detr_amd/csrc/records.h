@@ -1,7 +1,8 @@
 #pragma clang fp contract(off)
-// What the record kernels share (detections.hip, stage1_labels.hip; coco_eval.hip for the IoU alone): a device-resident store takes, per
-// image, wire records and evaluation records (cut at max_det) behind the records of the images before it.  Here are the deterministic
-// placement of an image's records, the evaluation record itself, the float64 IoU and the host-side check of a store's arguments.
+// What the record kernels share (detections.hip, stage1_labels.hip; coco_eval.hip for the IoU alone; nms.hip for the IoU, the score order
+// and the sum): a device-resident store takes, per image, wire records and evaluation records (cut at max_det) behind the records of the
+// images before it.  Here are the deterministic placement of an image's records, the evaluation record itself, the score key and its sort
+// in LDS, the float64 IoU and the host-side check of a store's arguments.
 //
 // Everything these kernels compute must EQUAL numpy on the host, so a product must never be contracted into an FMA with a later
 // operation: the first line switches contraction off from here to the end of every translation unit that includes this header.
@@ -27,6 +28,38 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) s += red[w];
     return s;
+}
+
+// ascending key = descending score, equal scores by ascending query: high half = the inverted image of the score under the
+// order-preserving map float -> uint32 (sign bit flipped for positives, all bits for negatives; -0 is made +0 first, the two compare equal)
+__device__ __forceinline__ unsigned long long sort_key(float p, int q) {
+    if (p == 0.0f) p = 0.0f;
+    unsigned u = __float_as_uint(p);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)(~u) << 32) | (unsigned)q;
+}
+
+// key[0 .. cnt) ascending, in place, by a workgroup of THREADS threads: bitonic sort over the next power of two, which `key` must hold
+// (the padding is ~0, above every sort_key).  Every thread calls this (it holds barriers); the keys must have been written before the
+// call by the threads that own them, no barrier needed in between.  Distinct keys: the result is the one sorted order.
+template <int THREADS>
+__device__ __forceinline__ void sort_keys(unsigned long long* key, int cnt) {
+    int npad = 1;
+    while (npad < cnt) npad <<= 1;
+    for (int i = cnt + threadIdx.x; i < npad; i += THREADS) key[i] = ~0ull;
+    __syncthreads();
+    for (int k2 = 2; k2 <= npad; k2 <<= 1) {
+        for (int j = k2 >> 1; j >= 1; j >>= 1) {
+            for (int i = threadIdx.x; i < npad; i += THREADS) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = key[i], c = key[l];
+                    if ((a > c) == ((i & k2) == 0)) { key[i] = c; key[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // where the records of image b of a call land, and whether they fit.  T = the type of the running sums: each kernel keeps the one it

@@ -709,6 +709,34 @@ int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream);
 int cdetr_count_sweep(const float* prob, const float* thresholds, int32_t B, int32_t Q, int32_t T, int32_t* table, int32_t N, int32_t first,
                       void* stream);
 
+/* ---- greedy non-maximum suppression ahead of the emit (csrc/nms.hip; infer.py --nms_iou): a FILTER on prob, EQUAL to the host rule of
+ * counting_detr_amd/nms.py; FMA contraction is switched off in this translation unit.
+ * cdetr_nms_suppress: ONE launch per forwarded batch, one workgroup per image.  The candidates of image b are the queries with
+ *   prob >= threshold in fp32 (a NaN is never one), walked by descending prob, equal probabilities in ascending query order (the order of the
+ *   evaluation records of cdetr_emit_detections, not cut at any max_det).  A candidate's box is its evaluation box, the integers
+ *   { tdiv2(2 cx - w), tdiv2(2 cy - h), w, h } of the truncated fp32 products with the original width / height, widened to float64.  A
+ *   candidate is suppressed when its IoU (coco_ap.box_iou_xywh: float64, the division performed, 0 where the union is not positive) with an
+ *   earlier SURVIVING candidate is > iou, strictly; a suppressed candidate suppresses nobody.
+ *     prob_out [B][Q]  prob with every suppressed entry replaced by a quiet NaN; every other entry keeps its bits (NaNs, -0 and everything
+ *                      below the threshold included).  Every entry is written once and none is read; prob_out must not alias prob.
+ *     removed [B]      suppressed candidates per image.
+ *   The sorted keys of an image (32 KiB at the limit), the 64 boxes of the chunk being resolved and one flag byte per query live in LDS, under
+ *   the 64 KiB static default; each thread keeps the boxes of its own <= 4 candidates in registers.  No atomics.  Limits: Q <= 4096,
+ *   B <= 65535, CDETR_ERR_UNSUPPORTED beyond; B, Q >= 1, a finite iou in [0, 1], a threshold that is not NaN and non-NULL pointers,
+ *   CDETR_ERR_ARG otherwise.  Nothing is launched on an error.                                                                          */
+typedef struct {
+    int32_t B, Q;               /* images in this batch, queries per image */
+    float threshold;            /* a query is a candidate when prob >= threshold */
+    int32_t pad_;
+    double iou;                 /* suppressed when the IoU with an earlier survivor is > iou */
+    const float* prob;          /* [B][Q] */
+    const float* boxes;         /* [B][Q][4] normalised cxcywh */
+    const int32_t* orig_hw;     /* [B][2] original (height, width) in pixels */
+    float* prob_out;            /* [B][Q] */
+    int32_t* removed;           /* [B] */
+} cdetr_nms_suppress_desc;
+int cdetr_nms_suppress(const cdetr_nms_suppress_desc* d, void* stream);
+
 /* ---- stage-1 pseudo labels emitted on the device (csrc/stage1_labels.hip): what the 1st stage's label writer does per annotated dot on the
  * host between the forward and pseudo_bbox_<split>.json (A1/engine.py:124-187; stage1.write_pseudo_labels' loop), plus the offline
  * evaluator's reading of that file (A1/offline_coco_evaluator.py:134-143: [cx, cy, w, h] -> a detection [cx - w/2, cy - h/2, w, h] of score

@@ -46,6 +46,14 @@ written predictions and the host matcher's flags (the checker); any other host-l
 `--device_detections` ONE cdetr_render_boxes launch reads the store's boxes and the flags of the split's one matching where they lie -- only the
 chosen images' pixels go up, only the overlays come back.  Same PNG bytes on every route.  Without the flags nothing changes.
 
+`--nms_iou T` (a number in [0, 1]; off without it) suppresses duplicate detections -- several query patterns of one anchor position firing on the same
+object -- before anything counts them: per image the queries at or above the pass's lowest threshold are walked by descending score and one whose
+evaluation box has an IoU > T with an earlier SURVIVING one is dropped (counting_detr_amd/nms.py states the rule).  It is a filter on `prob`: the
+suppressed queries become NaN directly after the forward, which the counting rule, the emit, the sweep's count and the host loop never keep, so
+--threshold, --sweep_thresholds, --image_report and --render_worst work on the survivors unchanged (greedy suppression is prefix-consistent: the
+filter at a sweep's lowest threshold is the filter of each of its thresholds).  The host loop calls nms.suppress (numpy, the checker); with
+--device_detections ONE cdetr_nms_suppress launch per batch does the same bit for bit.  The metrics gain nms_removed.  Without the flag nothing changes.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
@@ -54,6 +62,7 @@ chosen images' pixels go up, only the overlays come back.  Same PNG bytes on eve
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --sweep_thresholds 0.3:0.7:9
   python infer.py -dp /data/FSC147 --split test --resume out/detr_retrain.pth -o out --device_detections --threshold ckpt
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --eval_batch_size 16
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --nms_iou 0.5
 """
 import json
 import os
@@ -126,7 +135,7 @@ class Render:
 
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None):
+          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -145,9 +154,16 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     predictions file is; with `device_detections` and `gt_json` the statistics come from the store's ONE matching (one more launch),
     otherwise from the predictions as written.
     `render` (a Render; needs `image_report`): render_<split>/ with the overlays of the report's worst images is written wherever the
-    predictions file is, drawn where the pass matched: from the store's one matching, else from the predictions as written."""
+    predictions file is, drawn where the pass matched: from the store's one matching, else from the predictions as written.
+    `nms_iou` (--nms_iou; None: off, and nothing changes): greedy suppression of duplicate detections (counting_detr_amd/nms.py states the
+    rule).  Directly after the forward `prob` is replaced by the filtered tensor, suppressed queries NaN -- which no reader below counts --, at
+    the pass's lowest threshold (`threshold`, or the sweep's first); the host loop calls nms.suppress, the device loop launches
+    cdetr_nms_suppress once per batch.  The metrics gain `nms_removed`: the split's queries with raw prob >= `threshold` that were suppressed."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
+    if nms_iou is not None:
+        from counting_detr_amd import nms
+        nms_iou = nms.check_iou(nms_iou)
     if render is not None:
         if image_report is None:
             raise ValueError("infer: --render_worst / --render_ids draw what --image_report lists: pass an ImageReport as well")
@@ -170,7 +186,7 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
         out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report,
-                            render, output_dir)
+                            render, output_dir, nms_iou)
         _write_sweep(sweep, output_dir, split)
         if image_report is not None and output_path is not None:
             image_report.write(output_dir)
@@ -179,6 +195,7 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     anno_id = 1
     pred_counts, gt_counts, loss_sum, n_img = [], [], {}, 0
     tables, dt_by, image_ids = [], {}, []           # sweep: count rows per batch, the detections kept at the sweep's lowest threshold
+    nms_removed = 0
     def lookahead(loader):          # (batch on the device, the next batch's image tensor or None): the engine runs the next image's frozen
         prev = None                 # stage (stem + layer1) beside this image's encoder / decoder
         for cur in loader:
@@ -195,6 +212,13 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         rects = ret["ex_rects"].to(device)
         targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
         _, keep, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects, next_samples=next_image)      # forward + :75-81
+        if nms_iou is not None:                     # the filter: everything below reads the suppressed queries as NaN
+            raw = prob.cpu().numpy()
+            kept_h, _ = nms.suppress(raw, outputs["pred_boxes"].cpu().numpy(), [[int(x) for x in hw] for hw in ret["orig_size"]],
+                                     threshold if sweep is None else sweep.thresholds[0], nms_iou)
+            nms_removed += int((ts.kept(raw, threshold) & ~ts.kept(kept_h, threshold)).sum())
+            prob = torch.from_numpy(kept_h).to(prob.device)
+            keep = prob >= threshold
         if per_image:
             for k, v in criterion.per_image(outputs, targets).items():
                 for x in v.tolist():                # float(v[b]) in image order
@@ -240,6 +264,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     if n_img:       # images without objects contribute to MAE / RMSE only (the reference divides by the count, A2/eval_all.py:264-265)
         metrics.update(counting_metrics(pred_counts, gt_counts))
     metrics["images"] = n_img
+    if nms_iou is not None:
+        metrics["nms_removed"] = nms_removed
     if sweep is not None and n_img:
         import numpy as np
         ap_rows = None
@@ -276,7 +302,7 @@ def _num_images(data_loader):
 
 
 def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None,
-                  render=None, output_dir=None):
+                  render=None, output_dir=None, nms_iou=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -289,14 +315,16 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     from 1: the bytes of a pass without the sweep), the counts are the table's column at `threshold`, the AP of every threshold is a
     reading of that matching (`six_sweep`), the returned six numbers being its row at `threshold`, and the report and the overlays take the
     prefix of every image that `threshold` keeps, min(its count there, max_det).
-    Without `gt_json` the report and the overlays are formed from the predictions dict as written (`match_predictions`, once for both)."""
+    Without `gt_json` the report and the overlays are formed from the predictions dict as written (`match_predictions`, once for both).
+    `nms_iou`: one cdetr_nms_suppress launch per batch at the store's threshold replaces `prob` before the emit and the sweep's count read it;
+    the number of suppressed queries with raw prob >= `threshold` is accumulated in a device scalar and read after the loop."""
     import numpy as np
     from counting_detr_amd import ops
     from counting_detr_amd import threshold_sweep as ts
     if device.type != "cuda":
         raise RuntimeError(f"infer: device_detections runs HIP kernels, device={device} has none (the default is the host path)")
     N = _num_images(data_loader)
-    store = meta = loss_buf = loss_keys = table = None
+    store = meta = loss_buf = loss_keys = table = nms_removed = None
     n_targets, gt_counts, n_img, n_batch = [], [], 0, 0
     with torch.cuda.device(device):
         for ret in data_loader:
@@ -328,9 +356,17 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
                 rows[:, 2].copy_(torch.as_tensor(ret["image_id"]).reshape(B), non_blocking=True)
             else:
                 rows[:, 2].copy_(torch.arange(n_img, n_img + B))
-            store.emit(prob.contiguous(), outputs["pred_boxes"].contiguous(), ref_points.reshape(B, Q, 2).contiguous(), rows[:, :2].to(torch.int32))
+            prob, pred_boxes, orig_hw = prob.contiguous(), outputs["pred_boxes"].contiguous(), rows[:, :2].to(torch.int32)
+            if nms_iou is not None:                 # the filter: the emit and the count below read the suppressed queries as NaN
+                raw = prob
+                prob, removed = ops.nms_suppress(raw, pred_boxes, orig_hw, store.threshold, nms_iou)
+                if nms_removed is None:
+                    nms_removed = torch.zeros((), dtype=torch.int64, device=device)
+                # at the store's own threshold `removed` is the number; under a sweep only those the run's threshold would have kept count
+                nms_removed += removed.sum() if sweep is None else ((raw >= threshold) & ~(prob >= threshold)).sum()
+            store.emit(prob, pred_boxes, ref_points.reshape(B, Q, 2).contiguous(), orig_hw)
             if table is not None:
-                table.emit(prob.contiguous())
+                table.emit(prob)
             gt_counts += [int(t["boxes"].shape[0]) for t in targets]
             n_img += B
         predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
@@ -366,6 +402,8 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
         if n_img:
             metrics.update(counting_metrics(pred_counts, gt_counts))
         metrics["images"] = n_img
+        if nms_iou is not None:
+            metrics["nms_removed"] = int(nms_removed) if nms_removed is not None else 0
         ap_json = sweep.gt_json if sweep is not None and sweep.gt_json is not None else gt_json
         matching = counts = ap_rows = None
         if ap_json is not None and n_img:                   # the store's ONE matching: everything below reads it
@@ -454,7 +492,7 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
     render = build_render(args)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
-                       sweep=sweep, image_report=report, render=render)
+                       sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None))
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers

@@ -16,6 +16,7 @@ threshold follows the test_* keys as test_best_threshold / test_best_<metric> (t
 written from then on carries "count_threshold": {"metric", "threshold", "value", "epoch"}, which `infer.py --threshold ckpt` reads.
 --image_report reaches the same passes (infer.py): six average-recall keys behind the AP keys, image_report_<split>.json wherever the predictions file is written.
 --render_worst K / --render_ids (with --image_report) reach them too: render_<split>/ with the box overlays of the report's worst images, beside that file.
+--nms_iou T reaches them too: greedy suppression of duplicate detections ahead of everything that counts them (counting_detr_amd/nms.py), nms_removed in the metrics.
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --synthetic --no_aux_loss ...
@@ -200,7 +201,7 @@ def main(args):
             metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=_infer.run_threshold(args),
                                       device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
                                       per_image=per_image, sweep=_infer.build_sweep(args), image_report=_infer.build_image_report(args, device),
-                                      render=_infer.build_render(args))
+                                      render=_infer.build_render(args), nms_iou=getattr(args, "nms_iou", None))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
