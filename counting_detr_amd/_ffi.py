@@ -120,7 +120,7 @@ def nms_suppress_desc():
 EXPORTS = ["cdetr_gemm", "cdetr_gemm_dl", "cdetr_gemm_group", "cdetr_wgrad", "cdetr_wgrad_group", "cdetr_colsum", "cdetr_sumsq", "cdetr_adamw_step", "cdetr_adamw_step2", "cdetr_sgd_step", "cdetr_relu_mask", "cdetr_relu_mask2", "cdetr_layernorm_fwd", "cdetr_layernorm_fwd_add", "cdetr_layernorm_bwd", "cdetr_layernorm_bwd_merge", "cdetr_groupnorm_fwd", "cdetr_groupnorm_bwd", "cdetr_groupnorm_fwd_ws", "cdetr_groupnorm_bwd_ws", "cdetr_posadd2",
            "cdetr_hw_reduce", "cdetr_posadd2_hw_reduce", "cdetr_bcast_add2", "cdetr_bcast_add2_sum", "cdetr_add2", "cdetr_grad_merge", "cdetr_sine_embed", "cdetr_sine_embed_bwd", "cdetr_maxpool3x3s2", "cdetr_maxpool3x3s2_split", "cdetr_weight_mirror", "cdetr_weight_images", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_mha_fwd", "cdetr_mha_bwd", "cdetr_mha_fwd_lens", "cdetr_mha_bwd_lens", "cdetr_attn_fwd", "cdetr_attn_bwd",
            "cdetr_mask_prep", "cdetr_stem_pack", "cdetr_exemplar_fwd", "cdetr_exemplar_bwd", "cdetr_aggr_weight_fwd", "cdetr_aggr_weight_bwd",
-           "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_criterion_eval", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_bbox_criterion_lens_fwd", "cdetr_bbox_criterion_lens_bwd", "cdetr_box_iou_xywh", "cdetr_coco_match", "cdetr_coco_image_stats", "cdetr_render_boxes", "cdetr_image_prep", "cdetr_emit_detections", "cdetr_emit_pseudo_labels", "cdetr_count_sweep", "cdetr_nms_suppress", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
+           "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_criterion_eval", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_bbox_criterion_lens_fwd", "cdetr_bbox_criterion_lens_bwd", "cdetr_box_iou_xywh", "cdetr_coco_match", "cdetr_coco_image_stats", "cdetr_coco_errors", "cdetr_render_boxes", "cdetr_image_prep", "cdetr_emit_detections", "cdetr_emit_pseudo_labels", "cdetr_count_sweep", "cdetr_nms_suppress", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
 
 _lib = None
 
@@ -248,6 +248,8 @@ def lib():
         L.cdetr_coco_match.argtypes = [_p, _p]
         L.cdetr_coco_image_stats.restype = C.c_int
         L.cdetr_coco_image_stats.argtypes = [_p] * 7 + [C.c_int32] * 6 + [_p] * 4
+        L.cdetr_coco_errors.restype = C.c_int
+        L.cdetr_coco_errors.argtypes = [_p] * 8 + [C.c_int32] * 4 + [C.c_double] * 4 + [_p] * 8
         L.cdetr_render_boxes.restype = C.c_int
         L.cdetr_render_boxes.argtypes = [_p] * 15 + [C.c_int32] * 8 + [C.c_int64, _p, _p]
         L.cdetr_image_prep.restype = C.c_int

@@ -140,6 +140,13 @@ def get_args_parser():
                         "IoU > T is dropped (counting_detr_amd/nms.py states the rule).  T in [0, 1]; 1 suppresses nothing.  Works with --threshold, "
                         "--sweep_thresholds, --image_report and --render_worst; the metrics gain nms_removed.  With --device_detections: one "
                         "cdetr_nms_suppress launch per batch")
+    p.add_argument("--error_report", action="store_true", default=argparse.SUPPRESS,
+                   help="infer.py / main.py --eval / --eval_every: also say WHY detections fail -- the single-class TIDE breakdown at IoU 0.5: "
+                        "duplicate, localisation (0.1 <= IoU < 0.5), background and missed (counting_detr_amd/error_report.py states the rule).  "
+                        "error_report_<split>.json beside the predictions file (per image: the counts and mean IoUs; the images ordered by each "
+                        "cause; what AP50 would gain if a cause were fixed) and err_dup / err_loc / err_bkg / err_misloc / err_missed, dAP50_dup / "
+                        "_loc / _bkg / _missed in the metrics.  Needs instances_<split>.json, not --image_report.  On a CUDA device one "
+                        "cdetr_coco_errors launch for the split; --ap_on_host: the numpy rule, the same file")
     return p
 
 

@@ -27,7 +27,7 @@ ONE MATCHING, MANY READERS (`Matching`): the flags of a matching -- matched, det
 the device, `match_store` from an ops.DetectionStore (`pack_store` packs only the ground truths; the detections are read where
 cdetr_emit_detections, csrc/detections.hip, left them in evaluation order) and `match_predictions` from a predictions dict as written.  Its
 readings: `host()` (the flags in one copy, taken once), `six()` (`accumulate` = the tail of `average_precision` as array operations, the same
-float64 operations in the same order: EQUAL numbers), `six_sweep(thresholds)`, `stats(cuts, counts)` and `row50()` (render.py's overlays).
+float64 operations in the same order: EQUAL numbers), `six_sweep(thresholds)`, `stats(cuts, counts)`, `errors(counts)` and `row50()` (render.py's overlays).
 `summarize(device=)`, `summarize_store`, `summarize_store_sweep`, `image_stats` and `image_stats_store` are one maker and one reading each
 (tests/test_matching_cpu.py, test_coco_ap_device_gpu.py, test_detections_gpu.py).
 
@@ -43,6 +43,10 @@ image's own AP is `_sample` on its own list.  `stats_from_flags` states that in 
 cdetr_coco_image_stats launch (csrc/coco_report.hip) where they lie: EQUAL numbers, the average precisions bit for bit
 (tests/test_image_report_cpu.py, _gpu.py).  `average_recall`, `image_rows` and `image_report` turn the statistics into what is
 printed and written.
+
+ERROR BREAKDOWN (`errors`, infer.py --error_report): WHY a detection failed -- duplicate, localisation, background, missed -- as one more reading of a
+`Matching`: counting_detr_amd/error_report.py states the rule in numpy (host flags), device flags go through ONE cdetr_coco_errors launch
+(csrc/error_report.hip) on the boxes where they lie: EQUAL codes, the IoUs bit for bit (tests/test_error_report_cpu.py, _gpu.py).
 """
 import json
 
@@ -298,6 +302,33 @@ class Matching:
             tp, fp, ap = ops.coco_image_stats(self.matched, self.det_ignored, i[:B + 1], self.npig, i[B + 1:B + 1 + M], rec,
                                               dt_cnt=None if counts is None else i[B + 1 + M:], host=True)
         return _stats_dict(pack["image_ids"], tp, fp, ap, npig, cuts)
+
+    def errors(self, counts=None, iou_bg=0.1):
+        """-> the codes of error_report.classify (a dict of host arrays) for the pack, at area range `all` and IoU IOU_THRS[0], of the first
+        counts[k] detections of image k of `image_ids` where `counts` is given.  Host flags: the numpy rule itself.  Device flags: ONE
+        cdetr_coco_errors launch (csrc/error_report.hip) on the boxes where they lie -- a store's detections are not moved, the packed ground
+        truths go up again -- and one copy of the codes back: EQUAL arrays, the IoUs bit for bit."""
+        from . import error_report as er
+        pack, counts = self.pack, self.pack_counts(counts)
+        if self.device is None:
+            return er.classify(pack, counts, iou_bg)
+        import torch
+        from . import ops
+        B, G = len(pack["image_ids"]), len(pack["gt_area"])
+        dt_dev = pack.get("dt_device")
+        dt_host = (pack["dt_boxes"].reshape(-1), pack["dt_area"]) if dt_dev is None else (np.zeros(0), np.zeros(0))
+        f64 = np.concatenate([pack["gt_boxes"].reshape(-1), pack["gt_area"], dt_host[0], dt_host[1]])
+        i32 = np.concatenate([pack["gt_off"], pack["dt_off"], np.asarray([] if counts is None else counts, dtype=np.int64)]).astype(np.int32)
+        with torch.cuda.device(self.device):
+            f = torch.from_numpy(f64).to(self.device)
+            i = torch.from_numpy(i32).to(self.device)
+            ig = torch.from_numpy(pack["gt_ignore"]).to(self.device)
+            cuts = np.cumsum([0, 4 * G, G, len(dt_host[0]), len(dt_host[1])])
+            gt_boxes, gt_area, dt_boxes, dt_area = (f[cuts[k]:cuts[k + 1]] for k in range(4))
+            if dt_dev is not None:
+                dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
+            return ops.coco_errors(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:2 * B + 2], int(pack["g_max"]), er.IOU_FG, iou_bg,
+                                   AREA_RNG["all"], dt_cnt=None if counts is None else i[2 * B + 2:], host=True)
 
     def row50(self):
         """-> (matched, det_ignored) [D] at area range `all`, IoU 0.5, row [0, 0] of the flags, for the renderer: views of the device tensors

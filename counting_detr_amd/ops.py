@@ -2093,6 +2093,49 @@ def coco_image_stats(matched, det_ignored, dt_off, npig, cuts, rec_thrs, dt_cnt=
     return tp.view(A, B, T, M), fp.view(A, B, T, M), ap.view(A, B, T)
 
 
+def coco_errors(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, g_max, iou_fg, iou_bg, area_rng, dt_cnt=None, host=False,
+                events=None):
+    """cdetr_coco_errors: the error breakdown of B packed images in one launch (counting_detr_amd/error_report.py states the rule).  Device
+    tensors as for coco_match: float64 boxes [*, 4] / areas, uint8 ignore flags, int32 offset tables [B + 1], dt_cnt [B] or None = whole
+    segments; detections in evaluation order (a store's are read where cdetr_emit_detections left them); g_max = the largest ground-truth
+    count of one image, iou_fg / iou_bg and area_rng = (lo, hi) host numbers.  -> {"dt_code" u8 [D], "dt_gt" i32 [D], "dt_iou" f64 [D],
+    "gt_code" u8 [G], "gt_dt" i32 [G], "gt_iou" f64 [G], "counts" i32 [B, 9]}: views of ONE byte buffer; host=True returns them as numpy
+    arrays after a single copy.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/error_report_time.py)."""
+    _expect("coco_errors", torch.float64, gt_boxes=gt_boxes, gt_area=gt_area, dt_boxes=dt_boxes, dt_area=dt_area)
+    _expect("coco_errors", torch.uint8, gt_ignore=gt_ignore)
+    _expect("coco_errors", torch.int32, gt_off=gt_off, dt_off=dt_off, dt_cnt=dt_cnt)
+    dev = gt_off.device
+    B, G, D = gt_off.numel() - 1, gt_area.numel(), dt_area.numel()
+    if B < 0 or gt_boxes.numel() != 4 * G or gt_ignore.numel() != G or dt_boxes.numel() != 4 * D or dt_off.numel() != B + 1 \
+            or (dt_cnt is not None and dt_cnt.numel() != B):
+        raise RuntimeError("coco_errors: packed arrays of inconsistent sizes")
+    for name, t in (("gt_boxes", gt_boxes), ("gt_area", gt_area), ("gt_ignore", gt_ignore), ("dt_boxes", dt_boxes), ("dt_area", dt_area),
+                    ("dt_off", dt_off), ("dt_cnt", dt_cnt)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"coco_errors: `{name}` on {t.device}, gt_off on {dev}")
+    sections = [("dt_iou", 8, D), ("gt_iou", 8, G), ("dt_gt", 4, D), ("gt_dt", 4, G), ("counts", 4, 9 * B), ("dt_code", 1, D), ("gt_code", 1, G)]
+    cuts = [0]
+    for _, size, n in sections:
+        cuts.append(cuts[-1] + size * n)
+    buf = torch.empty(max(cuts[-1], 1), dtype=torch.uint8, device=dev)
+    kinds = {8: torch.float64, 4: torch.int32, 1: torch.uint8}
+    out = {name: buf[lo:lo + size * n].view(kinds[size]) for lo, (name, size, n) in zip(cuts, sections)}
+    p = lambda t, n: ptr(t) if n else None                                                # noqa: E731
+    with _between(events):
+        check(lib().cdetr_coco_errors(p(gt_boxes, G), p(gt_area, G), p(gt_ignore, G), ptr(gt_off), p(dt_boxes, D), p(dt_area, D), ptr(dt_off),
+                                      ptr(dt_cnt), B, G, D, int(g_max), float(iou_fg), float(iou_bg), float(area_rng[0]), float(area_rng[1]),
+                                      p(out["dt_code"], D), p(out["dt_gt"], D), p(out["dt_iou"], D), p(out["gt_code"], G), p(out["gt_dt"], G),
+                                      p(out["gt_iou"], G), ptr(out["counts"]), stream_ptr()), "cdetr_coco_errors")
+    if host:
+        h = buf.cpu().numpy()
+        np_kinds = {8: "float64", 4: "int32", 1: "uint8"}
+        out = {name: h[lo:lo + size * n].view(np_kinds[size]) for lo, (name, size, n) in zip(cuts, sections)}
+        out["counts"] = out["counts"].reshape(B, 9)
+        return out
+    out["counts"] = out["counts"].view(B, 9)
+    return out
+
+
 def render_boxes(pix, pix_off, size, sel, dt_boxes, dt_off, matched50, ignored50, gt_boxes, gt_off, ex_boxes, ex_off, style, dot=1, dt_cnt=None,
                  sel_host=None, max_hw=None, out=None, events=None):
     """cdetr_render_boxes: the box overlays of K canvases in one launch (counting_detr_amd/render.py states the rule).  Device tensors: uint8 pix

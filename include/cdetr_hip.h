@@ -572,6 +572,44 @@ int cdetr_coco_image_stats(const uint8_t* matched, const uint8_t* det_ignored,  
                            double* ap,                 /* [A][B][T] */
                            void* stream);
 
+/* ---- error breakdown (csrc/error_report.hip; infer.py --error_report): WHY a detection failed -- the single-class form of the TIDE
+ * breakdown, which the reference does not have: duplicate, localisation, background, missed.  counting_detr_amd/error_report.py states the
+ * rule in numpy; FLOAT64 and integers only, contraction into FMAs switched off, no atomics: every output EQUALS it bit for bit.
+ * cdetr_coco_errors: ONE launch, one workgroup per image.  Images are packed as for cdetr_coco_match (gt_off / dt_off, detections in
+ *   evaluation order); of image b the first n = min(dt_cnt[b], segment) detections are used (the whole segment without dt_cnt).  A ground truth
+ *   is ignored when gt_ignore is set or its area is < area_lo or > area_hi.  All indices below are LOCAL to the image.
+ *     the match    : cdetr_coco_match's greedy rule at the one threshold iou_fg (used as given), serial in the detections.
+ *     best overlap : of detection d, the largest IoU over the non-ignored ground truths, taken or not, the highest index among equal IoUs;
+ *                    (0.0, -1) when no IoU is > 0.
+ *     dt_code      : 0 TP matched to a non-ignored ground truth; 1 IGN matched to an ignored one, or unmatched with an area outside the range;
+ *                    else 2 DUP best >= iou_fg, 3 LOC iou_bg <= best < iou_fg, 4 BKG best < iou_bg; 255 beyond the prefix n.
+ *     dt_gt, dt_iou: the matched ground truth and the IoU with it; unmatched: the best overlap (-1 and 0.0 when there is none, and beyond n).
+ *     gt_code      : 1 IGN ignored; else 0 HIT matched; else 2 MISLOC the best overlap of at least one LOC detection; else 3 MISSED.
+ *     gt_iou, gt_dt: the ground truth's largest IoU over the used detections (ignored ground truths too) and the lowest detection that
+ *                    reaches it (-1 when it is 0); a HIT ground truth's gt_dt is the detection matched to it.
+ *     counts[b]    : { TP, IGN, DUP, LOC, BKG detections; HIT, IGN, MISLOC, MISSED ground truths }.
+ *   Wave 0 walks the greedy match (lanes over the ground truths, a taken-mask, a wave arg-max); the other 15 waves own the ground truths
+ *   in blocks of 64, form every IoU once, keep the per-ground-truth maxima in registers and reduce each detection's best overlap; chunks
+ *   of 64 detections are handed over through LDS and finished by one wave, the MISLOC marks set one detection after the other.
+ *   EVERY element of the seven outputs is written exactly once, except the elements of a segment that does not lie inside 0 .. Gtot /
+ *   0 .. Dtot or holds more than Gmax ground truths: such a segment counts as empty and is neither read nor written.
+ *   Gmax = the largest ground-truth count of one image (host-known: it sizes the LDS image; limit 4096, CDETR_ERR_UNSUPPORTED beyond,
+ *   before any launch); any number of detections.  B == 0: nothing is launched.  Gtot == 0 / Dtot == 0: their pointers may be NULL.
+ *   Negative sizes, a NaN among the four numbers or a NULL where data is required: CDETR_ERR_ARG, before any launch.                     */
+int cdetr_coco_errors(const double* gt_boxes,       /* [Gtot][4] xywh */
+                      const double* gt_area,        /* [Gtot] */
+                      const uint8_t* gt_ignore,     /* [Gtot] ignore or iscrowd */
+                      const int32_t* gt_off,        /* [B+1] */
+                      const double* dt_boxes,       /* [Dtot][4] xywh, evaluation order */
+                      const double* dt_area,        /* [Dtot] */
+                      const int32_t* dt_off,        /* [B+1] */
+                      const int32_t* dt_cnt,        /* [B] or NULL */
+                      int32_t B, int32_t Gtot, int32_t Dtot, int32_t Gmax, double iou_fg, double iou_bg, double area_lo, double area_hi,
+                      uint8_t* dt_code, int32_t* dt_gt, double* dt_iou,    /* [Dtot] */
+                      uint8_t* gt_code, int32_t* gt_dt, double* gt_iou,    /* [Gtot] */
+                      int32_t* counts,              /* [B][9] */
+                      void* stream);
+
 /* ---- box overlays drawn on the device (csrc/render.hip; infer.py --render_worst / --render_ids): what the reference's evaluators draw with
  * cv2.rectangle / cv2.circle under `visualize_res` and never save (L2/offline_lvis_evaluator.py:167-207), as ONE launch over the chosen images
  * of a split, from the boxes and the IoU-0.5 flags cdetr_coco_match left in device memory.  Integers and float64 only, contraction into FMAs

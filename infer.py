@@ -54,8 +54,18 @@ suppressed queries become NaN directly after the forward, which the counting rul
 filter at a sweep's lowest threshold is the filter of each of its thresholds).  The host loop calls nms.suppress (numpy, the checker); with
 --device_detections ONE cdetr_nms_suppress launch per batch does the same bit for bit.  The metrics gain nms_removed.  Without the flag nothing changes.
 
+`--error_report` says WHY detections fail, the single-class form of the TIDE breakdown at IoU 0.5 (counting_detr_amd/error_report.py states the rule): an
+unmatched detection is a duplicate (its best ground truth is taken), a localisation error (0.1 <= IoU < 0.5) or background; an unmatched ground truth is
+mislocalised or missed.  The metrics gain err_dup / err_loc / err_bkg / err_misloc / err_missed and dAP50_dup / _loc / _bkg / _missed (what AP50 would gain if
+the cause were fixed) and error_report_<split>.json appears beside the predictions file ({"split", "threshold", "iou_fg", "iou_bg", "max_dets", "totals",
+"dAP50", "rows", "order_by_dup", "order_by_loc", "order_by_bkg", "order_by_missed"}).  It needs instances_<split>.json, not --image_report; with both, the two
+reports read the same one matching.  With --device_detections ONE cdetr_coco_errors launch reads the store's boxes where they lie; any other run on a GPU packs
+the written predictions for the same kernel; `--ap_on_host` is the numpy rule.  Same bytes on every route; with --sweep_thresholds the report describes the
+run's own --threshold.  Without the flag nothing changes.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --error_report
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_worst 8
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_ids 3,17
@@ -101,6 +111,27 @@ class ImageReport:
                 json.dump(self.report, handle)
 
 
+class ErrorReport:
+    """--error_report for one pass, beside ImageReport and with its three routes: where the box ground truth is, where the host route matches
+    (`device`: a CUDA device, or None = the numpy rule of counting_detr_amd/error_report.py) and, after the pass, `report` = error_report.report's
+    dict (None for a pass without images)."""
+
+    def __init__(self, gt_json, device=None):
+        self.gt_json, self.device, self.split, self.report = gt_json, device, None, None
+
+    def from_matching(self, matching, counts, image_ids, threshold):
+        """The report of the images `image_ids` (in the order they were run) from the `errors()` reading of ONE coco_ap.Matching -> the metrics'
+        err_* and dAP50_* keys.  `counts`: the prefix lengths of `Matching.errors` (None: every detection the matching saw)."""
+        from counting_detr_amd import error_report as er
+        self.report = er.report(matching.pack, matching.errors(counts), image_ids, self.split, threshold)
+        return er.metrics(self.report)
+
+    def write(self, output_dir):
+        if self.report is not None:
+            with open(os.path.join(output_dir, "error_report_" + self.split + ".json"), "w") as handle:
+                json.dump(self.report, handle)
+
+
 class Render:
     """--render_worst K / --render_ids for one pass: the overlays of the images `render.select` picks from the pass's image report, written to
     render_<split>/ wherever the predictions file is (counting_detr_amd/render.py states the drawing rule).  `out_dir`: where the last pass
@@ -135,7 +166,7 @@ class Render:
 
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None):
+          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None, error_report=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -158,7 +189,11 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     `nms_iou` (--nms_iou; None: off, and nothing changes): greedy suppression of duplicate detections (counting_detr_amd/nms.py states the
     rule).  Directly after the forward `prob` is replaced by the filtered tensor, suppressed queries NaN -- which no reader below counts --, at
     the pass's lowest threshold (`threshold`, or the sweep's first); the host loop calls nms.suppress, the device loop launches
-    cdetr_nms_suppress once per batch.  The metrics gain `nms_removed`: the split's queries with raw prob >= `threshold` that were suppressed."""
+    cdetr_nms_suppress once per batch.  The metrics gain `nms_removed`: the split's queries with raw prob >= `threshold` that were suppressed.
+    `error_report` (an ErrorReport; None: off, and nothing changes): the metrics gain err_dup / err_loc / err_bkg / err_misloc / err_missed and the
+    four dAP50_* numbers, and error_report_<split>.json is written wherever the predictions file is.  It reads the SAME one matching as
+    `image_report` -- with `device_detections` and `gt_json` the store's (one cdetr_coco_errors launch on the boxes where they lie), otherwise
+    one of the predictions as written -- and does not need an image report."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
     if nms_iou is not None:
@@ -172,6 +207,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         ts.column(sweep.thresholds, threshold)              # raises unless the run's own threshold is one of the sweep's
     if image_report is not None:
         image_report.split, image_report.report = split, None
+    if error_report is not None:
+        error_report.split, error_report.report = split, None
     output_path = os.path.join(output_dir, "predictions_" + split + ".json") if write_json else None
     if output_path is not None and os.path.isfile(output_path):
         os.remove(output_path)
@@ -186,10 +223,12 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
         out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report,
-                            render, output_dir, nms_iou)
+                            render, output_dir, nms_iou, error_report)
         _write_sweep(sweep, output_dir, split)
         if image_report is not None and output_path is not None:
             image_report.write(output_dir)
+        if error_report is not None and output_path is not None:
+            error_report.write(output_dir)
         return out
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
@@ -275,12 +314,18 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows)
     _write_sweep(sweep, output_dir, split)
     if image_report is not None and n_img:
-        matching = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device)       # once, for the report and the overlays
+        matching = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device)       # once, for the reports and the overlays
         metrics.update(image_report.from_matching(matching, None, image_ids, gt_counts, pred_counts, threshold))
         if output_path is not None:
             image_report.write(output_dir)
             if render is not None:
                 render.from_matching(matching, None, image_report, output_dir, threshold)
+    if error_report is not None and n_img:
+        if image_report is None:                # no statistics asked for: the breakdown reads the boxes, one area range carries them
+            matching = match_predictions(predictions, error_report.gt_json, image_ids, error_report.device, ("all",))
+        metrics.update(error_report.from_matching(matching, None, image_ids, threshold))
+        if output_path is not None:
+            error_report.write(output_dir)
     return metrics, predictions
 
 
@@ -302,7 +347,7 @@ def _num_images(data_loader):
 
 
 def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None,
-                  render=None, output_dir=None, nms_iou=None):
+                  render=None, output_dir=None, nms_iou=None, error_report=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -414,14 +459,19 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
         if matching is not None and gt_json is not None:
             metrics.update(matching.six() if ap_rows is None else ap_rows[col])
-        if image_report is not None and n_img:
-            if gt_json is None:                             # no device matching asked for: the report is formed from the predictions as written
+        if (image_report is not None or error_report is not None) and n_img:
+            if gt_json is None:                             # no device matching asked for: the reports are formed from the predictions as written
                 if predictions is None:
-                    raise RuntimeError("infer: an image report without the device matching (gt_json) is formed from the predictions file: write_json=False")
-                matching, counts = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device), None
-            metrics.update(image_report.from_matching(matching, counts, image_ids, gt_counts, pred_counts, threshold))
-            if render is not None and output_path is not None:
-                render.from_matching(matching, counts, image_report, output_dir, threshold)
+                    raise RuntimeError("infer: a report without the device matching (gt_json) is formed from the predictions file: write_json=False")
+                src = image_report if image_report is not None else error_report
+                areas = () if image_report is not None else (("all",),)         # the breakdown alone reads the boxes: one area range carries them
+                matching, counts = match_predictions(predictions, src.gt_json, image_ids, src.device, *areas), None
+            if image_report is not None:
+                metrics.update(image_report.from_matching(matching, counts, image_ids, gt_counts, pred_counts, threshold))
+                if render is not None and output_path is not None:
+                    render.from_matching(matching, counts, image_report, output_dir, threshold)
+            if error_report is not None:
+                metrics.update(error_report.from_matching(matching, counts, image_ids, threshold))
     return metrics, predictions
 
 
@@ -490,14 +540,18 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
         sweep = build_sweep(args)
     report = build_image_report(args, device)
     render = build_render(args)
+    errors = build_error_report(args, device)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
-                       sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None))
+                       sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None), error_report=errors)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
         ap_device = device if device.type == "cuda" and not getattr(args, "ap_on_host", False) else None
         ar = {k: metrics.pop(k) for k in (report.report["AR"] if report is not None and report.report else ())}      # the AR keys follow the AP keys
+        if errors is not None and errors.report:                                                                      # and the breakdown's follow those
+            from counting_detr_amd.error_report import metrics as error_metrics
+            ar.update({k: metrics.pop(k) for k in error_metrics(errors.report)})
         metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
         metrics.update(ar)
     return metrics
@@ -516,6 +570,18 @@ def build_image_report(args, device=None):
     return ImageReport(gt_json, torch.device(device) if on_device else None)
 
 
+def build_error_report(args, device=None):
+    """--error_report -> an ErrorReport for one pass, or None without the flag, as `build_image_report`: a missing instances_<split>.json is an
+    error here, before anything runs; `device`: where a pass that does not read the device store classifies (a CUDA device unless --ap_on_host)."""
+    if not getattr(args, "error_report", False):
+        return None
+    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+    if not os.path.isfile(gt_json):
+        raise FileNotFoundError(f"--error_report needs the split's box ground truth: {gt_json} is not there")
+    on_device = device is not None and torch.device(device).type == "cuda" and not getattr(args, "ap_on_host", False)
+    return ErrorReport(gt_json, torch.device(device) if on_device else None)
+
+
 def build_render(args):
     """--render_worst K / --render_ids -> a Render for one pass, or None without either flag.  Both draw what --image_report lists: without
     it this is an error (the parser says so first; a namespace built by hand meets it here)."""
@@ -530,6 +596,7 @@ def main(args):
     device = torch.device(args.device)
     build_render(args)
     build_image_report(args)                                            # --image_report without instances_<split>.json: an error before anything is built
+    build_error_report(args)                                            # --error_report likewise
     model, criterion, _ = counting_detr_amd.build_model(args)
     model.to(device)
     if args.resume:

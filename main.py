@@ -16,6 +16,8 @@ threshold follows the test_* keys as test_best_threshold / test_best_<metric> (t
 written from then on carries "count_threshold": {"metric", "threshold", "value", "epoch"}, which `infer.py --threshold ckpt` reads.
 --image_report reaches the same passes (infer.py): six average-recall keys behind the AP keys, image_report_<split>.json wherever the predictions file is written.
 --render_worst K / --render_ids (with --image_report) reach them too: render_<split>/ with the box overlays of the report's worst images, beside that file.
+--error_report reaches them too: WHY detections fail (duplicate / localisation / background / missed, counting_detr_amd/error_report.py) -- err_* and dAP50_*
+in the metrics (test_err_* / test_dAP50_* in the epoch log), error_report_<split>.json wherever the predictions file is written.
 --nms_iou T reaches them too: greedy suppression of duplicate detections ahead of everything that counts them (counting_detr_amd/nms.py), nms_removed in the metrics.
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
@@ -88,6 +90,9 @@ def main(args):
     if getattr(args, "image_report", False) and not args.synthetic and (args.eval or args.eval_every > 0):
         import infer as _infer
         _infer.build_image_report(args)         # without instances_<split>.json: an error now, not after the epochs
+    if getattr(args, "error_report", False) and not args.synthetic and (args.eval or args.eval_every > 0):
+        import infer as _infer
+        _infer.build_error_report(args)         # likewise
     device = torch.device(args.device if not getattr(args, "distributed", False) else f"cuda:{args.gpu}")
     # every rank builds the SAME initial weights (the init draws from the global RNG); only the data order is rank-specific.
     # Trainer additionally broadcasts rank 0's parameters and buffers (what DistributedDataParallel does at construction).
@@ -201,7 +206,8 @@ def main(args):
             metrics, _ = _infer.infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=_infer.run_threshold(args),
                                       device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
                                       per_image=per_image, sweep=_infer.build_sweep(args), image_report=_infer.build_image_report(args, device),
-                                      render=_infer.build_render(args), nms_iou=getattr(args, "nms_iou", None))
+                                      render=_infer.build_render(args), nms_iou=getattr(args, "nms_iou", None),
+                                      error_report=_infer.build_error_report(args, device))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
