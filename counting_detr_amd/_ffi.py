@@ -1,127 +1,72 @@
-"""ctypes binding of libcdetr_hip.so (include/cdetr_hip.h).  No torch types cross the boundary: raw device
-pointers (tensor.data_ptr()), sizes and the current hipStream_t.
+"""ctypes binding of libcdetr_hip.so, DERIVED from include/cdetr_hip.h at import: the header is the one statement of the ABI.  No torch types
+cross the boundary: raw device pointers (tensor.data_ptr()), sizes and the current hipStream_t.
+
+What the reader below understands -- the subset of C the header is written in:
+  - `#define CDETR_<NAME> <integer literal | CDETR_<OTHER>>`            -> DEFINES["<NAME>"] (anything else, the include guard too, is skipped);
+  - `typedef struct { ... } cdetr_x_y;`                                 -> a ctypes.Structure `XY`, a module attribute, in header order;
+  - `int | const char* cdetr_name(<parameters> | void);`                -> EXPORTS, and restype / argtypes in lib();
+  - fields and parameters: `[const] T name`, `[const] T* name`, several names after one T; T one of _SCALARS or, by value, an earlier struct;
+    every pointer, struct pointers included, is a c_void_p (C.byref(desc) is passed); `static inline` helpers are not part of the ABI.
+No arrays, unions, bit-fields, enums or function pointers: a declaration outside the subset raises at import, naming itself -- whoever needs
+one extends this reader and the compiler-checked layout test (tests/test_abi.py) together.
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CDETR_LIB") or os.path.join(_HERE, "lib", "libcdetr_hip.so")      # CDETR_LIB: experiment builds (tools/)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cdetr_hip.h")
 
-ROWS_DENSE, ROWS_CONV_FWD, ROWS_CONV_DGRAD = 0, 1, 2
-_p = C.c_void_p
-
-
-class ConvGeom(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("Ha", C.c_int32), ("Wa", C.c_int32), ("Hc", C.c_int32), ("Wc", C.c_int32),
-                ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("dil", C.c_int32)]
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "float": C.c_float, "double": C.c_double}
+_DECL = re.compile(r"(?:const\s+)?(\w+)\b\s*(.*)", re.S)      # base type, then the declarators `* a`, `a, b`
+DEFINES, EXPORTS, _STRUCTS, _PROTOS = {}, [], {}, []          # _PROTOS: (name, restype, argtypes) per prototype
 
 
-class GemmDesc(C.Structure):
-    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("taps", C.c_int32), ("batch", C.c_int32),
-                ("b_layout", C.c_int32), ("relu", C.c_int32), ("precision", C.c_int32), ("out_scale", C.c_float),
-                ("A", _p), ("lda", C.c_int64), ("sA", C.c_int64),
-                ("B", _p), ("ldb", C.c_int64), ("sB", C.c_int64),
-                ("C", _p), ("ldc", C.c_int64), ("sC", C.c_int64),
-                ("w_scale", _p), ("bias", _p), ("resid", _p), ("ldr", C.c_int64), ("gate", _p), ("ldg", C.c_int64),
-                ("g", ConvGeom), ("B_split", _p), ("batch_inner", C.c_int32), ("flags", C.c_int32),
-                ("sA2", C.c_int64), ("sB2", C.c_int64), ("sC2", C.c_int64), ("A16", _p), ("C16", _p),
-                ("splitk_ws", _p), ("splitk_ws_bytes", C.c_int64), ("A16lo", _p), ("B16", _p), ("gate16", _p), ("C16lo", _p)]
+def _ctypes_of(decl, where):
+    """`const float* A` / `int32_t Ha, Wa` / `cdetr_conv_geom g` -> [(name, ctype)]."""
+    base, rest = _DECL.fullmatch(decl.strip()).groups()
+    out = []
+    for d in rest.split(","):
+        m = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*", d)
+        if m is None or (not m.group(1) and base not in _SCALARS and base not in _STRUCTS):
+            raise RuntimeError(f"{HEADER_PATH}: `{decl.strip()}` in {where} is outside the subset counting_detr_amd/_ffi.py reads")
+        out.append((m.group(2), C.c_void_p if m.group(1) else _SCALARS.get(base) or _STRUCTS[base]))
+    return out
 
 
-class WgradDesc(C.Structure):
-    _fields_ = [("P", C.c_int32), ("Nout", C.c_int32), ("Cin", C.c_int32), ("taps", C.c_int32), ("batch", C.c_int32), ("precision", C.c_int32),
-                ("dY", _p), ("ldy", C.c_int64), ("sY", C.c_int64),
-                ("X", _p), ("ldx", C.c_int64), ("sX", C.c_int64),
-                ("dW", _p), ("ldw", C.c_int64), ("sW", C.c_int64),
-                ("w_scale", _p), ("dbias", _p), ("g", ConvGeom), ("batch_inner", C.c_int32), ("wg_target", C.c_int32),
-                ("sY2", C.c_int64), ("sX2", C.c_int64), ("sW2", C.c_int64), ("dY16", _p), ("X16", _p)]
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the binding of libcdetr_hip.so is derived from it")
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER_PATH).read(), flags=re.S)
+    raw = dict(re.findall(r"^[ \t]*#define[ \t]+CDETR_(\w+)[ \t]+(\w+)[ \t]*$", src, flags=re.M))
+    for name, v in raw.items():
+        for _ in raw:                                       # a define may name another
+            v = raw.get(v[len("CDETR_"):], v) if v.startswith("CDETR_") else v
+        if re.fullmatch(r"\d+|0[xX][0-9a-fA-F]+", v):
+            DEFINES[name] = int(v, 0)
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        fields = [f for decl in body.split(";") if decl.strip() for f in _ctypes_of(decl, name)]
+        camel = "".join(w.capitalize() for w in name[len("cdetr_"):].split("_"))
+        _STRUCTS[name] = globals()[camel] = type(camel, (C.Structure,), {"_fields_": fields})
+    for ret, name, params in re.findall(r"^[ \t]*([\w \t\*]+?)[ \t]*\b(cdetr_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        ret = re.sub(r"\s+", "", ret)
+        if ret not in ("int", "constchar*"):
+            raise RuntimeError(f"{HEADER_PATH}: return type of {name} is outside the subset counting_detr_amd/_ffi.py reads")
+        args = [] if params.strip() in ("", "void") else [_ctypes_of(p, name)[0][1] for p in params.split(",")]
+        EXPORTS.append(name)
+        _PROTOS.append((name, C.c_int if ret == "int" else C.c_char_p, args))
+    declared = re.findall(r"^(?!\s*static\b)[^\n(]*\b(cdetr_\w+)\s*\(", src, flags=re.M)
+    if declared != EXPORTS:
+        raise RuntimeError(f"{HEADER_PATH}: the declaration of {sorted(set(declared) ^ set(EXPORTS))} is outside the subset counting_detr_amd/_ffi.py reads")
 
 
-class RcdaFwdDesc(C.Structure):
-    _fields_ = [("N", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("nh", C.c_int32),
-                ("precision", C.c_int32), ("scale", C.c_float), ("q_row", _p), ("q_col", _p), ("k_row", _p), ("k_col", _p), ("v", _p),
-                ("mask_row", _p), ("mask_col", _p), ("out", _p), ("a_row", _p), ("a_col", _p), ("ws", _p), ("ws_bytes", C.c_int64)]
-
-
-class RcdaBwdDesc(C.Structure):
-    _fields_ = [("N", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("nh", C.c_int32),
-                ("precision", C.c_int32), ("scale", C.c_float), ("d_out", _p), ("a_row", _p), ("a_col", _p), ("v", _p),
-                ("ds_row", _p), ("ds_col", _p), ("d_v", _p), ("k_row", _p), ("k_col", _p), ("dq_row", _p), ("dq_col", _p),
-                ("q_row", _p), ("q_col", _p), ("dk_row", _p), ("dk_col", _p)]
-
-
-class AttnDesc(C.Structure):
-    _fields_ = [("q", _p), ("k", _p), ("v", _p), ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("o", _p), ("lse", _p),
-                ("d_o", _p), ("d_q", _p), ("d_k", _p), ("d_v", _p), ("ld_dq", C.c_int64), ("ld_dk", C.c_int64), ("ld_dv", C.c_int64),
-                ("work", _p), ("N", C.c_int32), ("Lq", C.c_int32), ("Lk", C.c_int32), ("nh", C.c_int32), ("scale", C.c_float),
-                ("precision", C.c_int32)]
-
-
-class CriterionDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("Q", C.c_int32), ("C", C.c_int32), ("num_classes", C.c_int32), ("Mmax", C.c_int32), ("alpha", C.c_float),
-                ("logits", _p), ("boxes", _p), ("vars", _p), ("tgt_boxes", _p), ("tgt_labels", _p), ("tgt_off", _p), ("idx_i", _p),
-                ("idx_j", _p), ("num_boxes", _p), ("losses", _p), ("g_logits", _p), ("g_l1", _p), ("g_giou", _p), ("g_var_box", _p),
-                ("g_vars", _p), ("loss_weights", _p)]
-
-
-class CriterionEvalDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("Q", C.c_int32), ("C", C.c_int32), ("num_classes", C.c_int32), ("Mmax", C.c_int32), ("alpha", C.c_float),
-                ("logits", _p), ("boxes", _p), ("vars", _p), ("tgt_boxes", _p), ("tgt_labels", _p), ("tgt_off", _p), ("idx_i", _p),
-                ("idx_j", _p), ("losses", _p), ("loss_weights", _p)]
-
-
-class MirrorItem(C.Structure):
-    _fields_ = [("src", _p), ("dst", _p), ("dst_split", _p), ("scale", _p), ("R", C.c_int32), ("C", C.c_int32), ("taps", C.c_int32),
-                ("tile0", C.c_int32), ("transpose", C.c_int32), ("pad_", C.c_int32), ("dst_hi", _p)]
-
-
-class CocoMatchDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("A", C.c_int32), ("T", C.c_int32), ("Gtot", C.c_int32), ("Dtot", C.c_int32), ("Gmax", C.c_int32),
-                ("gt_boxes", _p), ("gt_area", _p), ("gt_ignore", _p), ("gt_off", _p), ("dt_boxes", _p), ("dt_area", _p), ("dt_off", _p),
-                ("iou_thrs", _p), ("area_rng", _p), ("matched", _p), ("det_ignored", _p), ("npig", _p)]
-
-
-class ImagePrepDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("Hm", C.c_int32), ("Wm", C.c_int32), ("max_taps", C.c_int32), ("max_rows", C.c_int32), ("pad_", C.c_int32),
-                ("pixels", _p), ("pixel_bytes", C.c_int64), ("images", _p), ("tables", _p), ("table_ints", C.c_int64), ("lut", _p),
-                ("image", _p), ("mask", _p)]
-
-
-class EmitDetectionsDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("Q", C.c_int32), ("N", C.c_int32), ("first", C.c_int32), ("max_det", C.c_int32), ("wire_cap", C.c_int32),
-                ("eval_cap", C.c_int32), ("threshold", C.c_float), ("prob", _p), ("boxes", _p), ("points", _p), ("orig_hw", _p), ("counts", _p),
-                ("wire_off", _p), ("eval_off", _p), ("wire", _p), ("eval_boxes", _p), ("eval_area", _p), ("eval_score", _p), ("status", _p)]
-
-
-class EmitPseudoLabelsDesc(C.Structure):
-    _fields_ = [("B", C.c_int32), ("R", C.c_int32), ("N", C.c_int32), ("first", C.c_int32), ("max_det", C.c_int32), ("row_cap", C.c_int32),
-                ("eval_cap", C.c_int32), ("pad_", C.c_int32), ("points", _p), ("pred_wh", _p), ("counts", _p), ("orig_wh", _p), ("gt_xywh", _p),
-                ("img_counts", _p), ("row_off", _p), ("eval_off", _p), ("wire", _p), ("pair_iou", _p), ("eval_boxes", _p), ("eval_area", _p),
-                ("eval_score", _p), ("status", _p)]
-
-
-# cdetr_nms_suppress_desc, field for field; `nms_suppress_desc()` makes one (the twin class is built on first use and kept)
-NMS_SUPPRESS_FIELDS = [("B", C.c_int32), ("Q", C.c_int32), ("threshold", C.c_float), ("pad_", C.c_int32), ("iou", C.c_double),
-                       ("prob", _p), ("boxes", _p), ("orig_hw", _p), ("prob_out", _p), ("removed", _p)]
-_desc_types = {}
-
-
-def nms_suppress_desc():
-    """A zeroed cdetr_nms_suppress_desc."""
-    if "nms" not in _desc_types:
-        _desc_types["nms"] = type("NmsSuppressDesc", (C.Structure,), {"_fields_": NMS_SUPPRESS_FIELDS})
-    return _desc_types["nms"]()
-
-
-EXPORTS = ["cdetr_gemm", "cdetr_gemm_dl", "cdetr_gemm_group", "cdetr_wgrad", "cdetr_wgrad_group", "cdetr_colsum", "cdetr_sumsq", "cdetr_adamw_step", "cdetr_adamw_step2", "cdetr_sgd_step", "cdetr_relu_mask", "cdetr_relu_mask2", "cdetr_layernorm_fwd", "cdetr_layernorm_fwd_add", "cdetr_layernorm_bwd", "cdetr_layernorm_bwd_merge", "cdetr_groupnorm_fwd", "cdetr_groupnorm_bwd", "cdetr_groupnorm_fwd_ws", "cdetr_groupnorm_bwd_ws", "cdetr_posadd2",
-           "cdetr_hw_reduce", "cdetr_posadd2_hw_reduce", "cdetr_bcast_add2", "cdetr_bcast_add2_sum", "cdetr_add2", "cdetr_grad_merge", "cdetr_sine_embed", "cdetr_sine_embed_bwd", "cdetr_maxpool3x3s2", "cdetr_maxpool3x3s2_split", "cdetr_weight_mirror", "cdetr_weight_images", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_mha_fwd", "cdetr_mha_bwd", "cdetr_mha_fwd_lens", "cdetr_mha_bwd_lens", "cdetr_attn_fwd", "cdetr_attn_bwd",
-           "cdetr_mask_prep", "cdetr_stem_pack", "cdetr_exemplar_fwd", "cdetr_exemplar_bwd", "cdetr_aggr_weight_fwd", "cdetr_aggr_weight_bwd",
-           "cdetr_box_head_fwd", "cdetr_box_head_bwd", "cdetr_match_cost", "cdetr_lsap", "cdetr_criterion_fwd", "cdetr_criterion_bwd", "cdetr_criterion_eval", "cdetr_bbox_criterion_fwd", "cdetr_bbox_criterion_bwd", "cdetr_bbox_criterion_lens_fwd", "cdetr_bbox_criterion_lens_bwd", "cdetr_box_iou_xywh", "cdetr_coco_match", "cdetr_coco_image_stats", "cdetr_coco_errors", "cdetr_render_boxes", "cdetr_image_prep", "cdetr_emit_detections", "cdetr_emit_pseudo_labels", "cdetr_count_sweep", "cdetr_nms_suppress", "cdetr_last_error", "cdetr_abi_version", "cdetr_delay", "cdetr_flag_signal", "cdetr_flag_wait"]
-
+_read_header()
+ROWS_DENSE, ROWS_CONV_FWD, ROWS_CONV_DGRAD = DEFINES["ROWS_DENSE"], DEFINES["ROWS_CONV_FWD"], DEFINES["ROWS_CONV_DGRAD"]
 _lib = None
 
 
@@ -133,136 +78,13 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m counting_detr_amd.build` "
                                "(the Counting-DETR MI355X path has no fallback implementation)")
         L = C.CDLL(LIB_PATH)
-        L.cdetr_last_error.restype = C.c_char_p
-        L.cdetr_abi_version.restype = C.c_int
-        L.cdetr_gemm_dl.restype = C.c_int
-        L.cdetr_gemm_dl.argtypes = [_p, C.c_int32, C.c_int32, _p]
-        for name in ("cdetr_gemm", "cdetr_wgrad", "cdetr_rcda_fwd", "cdetr_rcda_bwd", "cdetr_attn_fwd", "cdetr_attn_bwd"):
-            getattr(L, name).restype = C.c_int
-            getattr(L, name).argtypes = [_p, _p]
-        L.cdetr_delay.restype = C.c_int
-        L.cdetr_delay.argtypes = [C.c_int32, _p]
-        L.cdetr_flag_signal.restype = C.c_int
-        L.cdetr_flag_signal.argtypes = [_p, _p]
-        L.cdetr_flag_wait.restype = C.c_int
-        L.cdetr_flag_wait.argtypes = [_p, _p, C.c_int32, C.c_int32, _p]
-        L.cdetr_gemm_group.restype = C.c_int
-        L.cdetr_gemm_group.argtypes = [_p, C.c_int32, _p]
-        L.cdetr_wgrad_group.restype = C.c_int
-        L.cdetr_wgrad_group.argtypes = [_p, C.c_int32, _p]
-        L.cdetr_colsum.restype = C.c_int
-        L.cdetr_colsum.argtypes = [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p]
-        L.cdetr_sumsq.restype = C.c_int
-        L.cdetr_sumsq.argtypes = [_p, C.c_int64, _p, _p, _p]
-        L.cdetr_adamw_step.restype = C.c_int
-        L.cdetr_adamw_step.argtypes = [_p, _p, _p, _p, _p, C.c_int64, _p, _p] + [C.c_float] * 6 + [_p]
-        L.cdetr_adamw_step2.restype = C.c_int
-        L.cdetr_adamw_step2.argtypes = [_p] * 5 + [C.c_float, C.c_float, C.c_int64, C.c_int64, _p, _p] + [C.c_float] * 6 + [_p]
-        L.cdetr_sgd_step.restype = C.c_int
-        L.cdetr_sgd_step.argtypes = [_p] * 4 + [C.c_float, C.c_float, C.c_int64, C.c_int64, _p, _p] + [C.c_float] * 4 + [_p]
-        L.cdetr_relu_mask.restype = C.c_int
-        L.cdetr_relu_mask.argtypes = [_p, _p, _p, C.c_int64, C.c_float, _p]
-        L.cdetr_relu_mask2.restype = C.c_int
-        L.cdetr_relu_mask2.argtypes = [_p, _p, _p, _p, C.c_int64, C.c_float, _p]
-        L.cdetr_layernorm_fwd.restype = C.c_int
-        L.cdetr_layernorm_fwd.argtypes = [_p] * 6 + [C.c_int32, C.c_int32, C.c_float, _p]
-        L.cdetr_layernorm_fwd_add.restype = C.c_int
-        L.cdetr_layernorm_fwd_add.argtypes = [_p] * 10 + [C.c_int32, C.c_int32, C.c_float, _p]
-        L.cdetr_layernorm_bwd.restype = C.c_int
-        L.cdetr_layernorm_bwd.argtypes = [_p] * 9 + [C.c_int32, C.c_int32, _p, _p]
-        L.cdetr_layernorm_bwd_merge.restype = C.c_int
-        L.cdetr_layernorm_bwd_merge.argtypes = [_p] * 7 + [C.c_float, C.c_float, C.c_int32, C.c_int32] + [_p] * 8 + [C.c_int32, C.c_int32, _p, _p]
-        L.cdetr_groupnorm_fwd.restype = C.c_int
-        L.cdetr_groupnorm_fwd.argtypes = [_p] * 6 + [C.c_int32] * 4 + [C.c_float, _p]
-        L.cdetr_groupnorm_bwd.restype = C.c_int
-        L.cdetr_groupnorm_bwd.argtypes = [_p] * 8 + [C.c_int32] * 4 + [_p]
-        L.cdetr_groupnorm_fwd_ws.restype = C.c_int
-        L.cdetr_groupnorm_fwd_ws.argtypes = [_p] * 6 + [C.c_int32] * 4 + [C.c_float, _p, C.c_int64, _p]
-        L.cdetr_groupnorm_bwd_ws.restype = C.c_int
-        L.cdetr_groupnorm_bwd_ws.argtypes = [_p] * 8 + [C.c_int32] * 4 + [_p, C.c_int64, _p]
-        L.cdetr_posadd2.restype = C.c_int
-        L.cdetr_posadd2.argtypes = [_p] * 5 + [C.c_int32] * 4 + [_p]
-        L.cdetr_posadd2_hw_reduce.restype = C.c_int
-        L.cdetr_posadd2_hw_reduce.argtypes = [_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_float, _p]
-        L.cdetr_hw_reduce.restype = C.c_int
-        L.cdetr_hw_reduce.argtypes = [_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_float, _p]
-        L.cdetr_criterion_fwd.restype = C.c_int
-        L.cdetr_criterion_fwd.argtypes = [_p, _p]
-        L.cdetr_criterion_bwd.restype = C.c_int
-        L.cdetr_criterion_bwd.argtypes = [_p] * 11 + [C.c_int32, C.c_int32, _p]
-        L.cdetr_criterion_eval.restype = C.c_int
-        L.cdetr_criterion_eval.argtypes = [_p, _p]
-        L.cdetr_bbox_criterion_fwd.restype = C.c_int
-        L.cdetr_bbox_criterion_fwd.argtypes = [_p, C.c_int64, _p, _p, C.c_int32, C.c_float, C.c_float, _p, _p, _p, _p]
-        L.cdetr_bbox_criterion_bwd.restype = C.c_int
-        L.cdetr_bbox_criterion_bwd.argtypes = [_p, C.c_float, C.c_float, _p, _p, _p, C.c_int32, _p]
-        L.cdetr_bbox_criterion_lens_fwd.restype = C.c_int
-        L.cdetr_bbox_criterion_lens_fwd.argtypes = [_p, C.c_int64, _p, _p, _p, C.c_int32, C.c_int32, C.c_float, C.c_float, _p, _p, _p, _p]
-        L.cdetr_bbox_criterion_lens_bwd.restype = C.c_int
-        L.cdetr_bbox_criterion_lens_bwd.argtypes = [_p, C.c_float, C.c_float, _p, _p, _p, _p, C.c_int32, C.c_int32, _p]
-        L.cdetr_sine_embed.argtypes = [_p, C.c_int32, _p, C.c_int64, C.c_int32, C.c_int32, C.c_float, _p]
-        L.cdetr_sine_embed_bwd.restype = C.c_int
-        L.cdetr_sine_embed_bwd.argtypes = [_p, C.c_int32, _p, C.c_int64, _p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _p]
-        L.cdetr_add2.restype = C.c_int
-        L.cdetr_add2.argtypes = [_p] * 5 + [C.c_int64, _p]
-        L.cdetr_grad_merge.restype = C.c_int
-        L.cdetr_grad_merge.argtypes = [_p] * 6 + [C.c_int64, _p]
-        L.cdetr_weight_images.restype = C.c_int
-        L.cdetr_weight_images.argtypes = [_p, C.c_int32, C.c_int32, _p]
-        L.cdetr_weight_mirror.restype = C.c_int
-        L.cdetr_weight_mirror.argtypes = [_p, C.c_int32, C.c_int32, _p]
-        L.cdetr_bcast_add2.restype = C.c_int
-        L.cdetr_bcast_add2.argtypes = [_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_float, _p]
-        L.cdetr_bcast_add2_sum.restype = C.c_int
-        L.cdetr_bcast_add2_sum.argtypes = [_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_float, _p]
-        L.cdetr_maxpool3x3s2.restype = C.c_int
-        L.cdetr_maxpool3x3s2.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
-        L.cdetr_maxpool3x3s2_split.restype = C.c_int
-        L.cdetr_maxpool3x3s2_split.argtypes = [_p, _p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p]
-        L.cdetr_mha_fwd.restype = C.c_int
-        L.cdetr_mha_fwd.argtypes = [_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_int32, _p]
-        L.cdetr_mha_bwd.restype = C.c_int
-        L.cdetr_mha_bwd.argtypes = [_p] * 8 + [C.c_int32] * 3 + [C.c_float, C.c_int32, _p]
-        L.cdetr_mha_fwd_lens.restype = C.c_int
-        L.cdetr_mha_fwd_lens.argtypes = [_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_int32, _p]
-        L.cdetr_mha_bwd_lens.restype = C.c_int
-        L.cdetr_mha_bwd_lens.argtypes = [_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_int32, _p]
-        L.cdetr_match_cost.restype = C.c_int
-        L.cdetr_match_cost.argtypes = [_p, C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                       C.c_float, _p, _p]
-        L.cdetr_lsap.restype = C.c_int
-        L.cdetr_lsap.argtypes = [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p, _p]
-        for name, args in (("cdetr_mask_prep", [_p] + [C.c_int32] * 5 + [_p] * 7),
-                           ("cdetr_stem_pack", [_p, _p] + [C.c_int32] * 7 + [_p]),
-                           ("cdetr_exemplar_fwd", [_p, _p, _p] + [C.c_int32] * 6 + [_p] * 4),
-                           ("cdetr_exemplar_bwd", [_p] * 4 + [C.c_int32] * 4 + [_p]),
-                           ("cdetr_aggr_weight_fwd", [_p] * 4 + [C.c_int32] * 3 + [_p]),
-                           ("cdetr_aggr_weight_bwd", [_p] * 5 + [C.c_int32] * 3 + [_p]),
-                           ("cdetr_box_head_fwd", [_p] * 3 + [C.c_int32] * 2 + [_p]),
-                           ("cdetr_box_head_bwd", [_p] * 5 + [C.c_int32] * 2 + [_p])):
-            getattr(L, name).restype = C.c_int
-            getattr(L, name).argtypes = args
-        L.cdetr_box_iou_xywh.restype = C.c_int
-        L.cdetr_box_iou_xywh.argtypes = [_p, C.c_int32, _p, C.c_int32, _p, _p]
-        L.cdetr_coco_match.restype = C.c_int
-        L.cdetr_coco_match.argtypes = [_p, _p]
-        L.cdetr_coco_image_stats.restype = C.c_int
-        L.cdetr_coco_image_stats.argtypes = [_p] * 7 + [C.c_int32] * 6 + [_p] * 4
-        L.cdetr_coco_errors.restype = C.c_int
-        L.cdetr_coco_errors.argtypes = [_p] * 8 + [C.c_int32] * 4 + [C.c_double] * 4 + [_p] * 8
-        L.cdetr_render_boxes.restype = C.c_int
-        L.cdetr_render_boxes.argtypes = [_p] * 15 + [C.c_int32] * 8 + [C.c_int64, _p, _p]
-        L.cdetr_image_prep.restype = C.c_int
-        L.cdetr_image_prep.argtypes = [_p, _p]
-        L.cdetr_emit_detections.restype = C.c_int
-        L.cdetr_emit_detections.argtypes = [_p, _p]
-        L.cdetr_emit_pseudo_labels.restype = C.c_int
-        L.cdetr_emit_pseudo_labels.argtypes = [_p, _p]
-        L.cdetr_count_sweep.restype = C.c_int
-        L.cdetr_count_sweep.argtypes = [_p, _p, C.c_int32, C.c_int32, C.c_int32, _p, C.c_int32, C.c_int32, _p]
-        L.cdetr_nms_suppress.restype = C.c_int
-        L.cdetr_nms_suppress.argtypes = [_p, _p]
-        if L.cdetr_abi_version() != 2:
+        for name, restype, argtypes in _PROTOS:
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/cdetr_hip.h declares: rebuild it with "
+                                   "`python -m counting_detr_amd.build`")
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.cdetr_abi_version() != DEFINES["ABI_VERSION"]:
             raise RuntimeError("libcdetr_hip.so ABI version mismatch")
         _lib = L
     return _lib

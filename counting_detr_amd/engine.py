@@ -17,6 +17,7 @@ import sys
 import torch
 import torch.distributed as dist
 
+from . import _ffi
 from . import backbone as _bb
 from .misc import NestedTensor, get_world_size, is_dist_avail_and_initialized, nested_tensor_from_tensor_list, reduce_dict
 
@@ -105,7 +106,6 @@ class FlatGradExchange:
             return e
         if get_world_size() < 2:
             if self.dummy_us > 0 and self.stream is not None:       # same ordering as a real bucket, an idle kernel instead of the collective
-                from . import _ffi
                 if side:                                            # issued from `also`; the idle kernel runs on the stand-in for RCCL's own stream
                     if self._pg_stream is None:
                         self._pg_stream = self.stream
@@ -379,7 +379,7 @@ class Trainer:
         self._one = torch.ones((), device=self.device)
         self._side = None
         self.sumsq = torch.zeros(1, device=self.device)
-        self.sumsq_ws = torch.zeros(2048, device=self.device)       # CDETR_SUMSQ_WS_FLOATS: per-block partial sums
+        self.sumsq_ws = torch.zeros(_ffi.DEFINES["SUMSQ_WS_FLOATS"], device=self.device)       # per-block partial sums
         self.epoch = 0
         self._entry = None                      # capture() / replay(): the explicitly captured step
         self._cap_stream = None
@@ -487,7 +487,6 @@ class Trainer:
     def _optimizer_step(self):
         """clip_grad_norm_(max_norm) + AdamW (or SGD) over the flat arenas: one reduction pass + one fused update pass
         (cdetr_sumsq / cdetr_adamw_step2 or cdetr_sgd_step); step count, StepLR factor and the norm stay on the device."""
-        from . import _ffi
         n = self.flat_p.numel()
         b1, b2 = self.betas
         st = _ffi.stream_ptr()
@@ -1025,7 +1024,6 @@ class Trainer:
         with torch.cuda.stream(ps):
             fs["images"].copy_(images, non_blocking=True)
             if self._pf_delay_us > 0 and not ordered:     # the solve first (it needs a whole CU's LDS), the flood of stem / layer1 workgroups after it
-                from . import _ffi
                 _ffi.check(_ffi.lib().cdetr_delay(self._pf_delay_us, _ffi.stream_ptr()), "cdetr_delay")
             if self._pf_eager:                 # stream-ordered launches instead of the graph (A/B: CDETR_PF_EAGER)
                 from . import ops
@@ -1372,7 +1370,6 @@ class Trainer:
 
     def _run_entry(self, e, announce):
         """announce = (image tensor of the next batch, its token) or None."""
-        from . import _ffi
         dp = self.exchange.active()
         inj = self._inject
 
@@ -1761,7 +1758,6 @@ def count_from_logits(pred_logits, threshold=0.5):
 def warm_streams(streams):
     """One trivial kernel per stream, then a device sync.  The FIRST launch on a fresh stream takes 0.2-40 ms (the runtime creates / binds its
     hardware queue then: `tools/probe_streams.py`) -- probed cold, a concurrent stream looks serialised."""
-    from . import _ffi
     for c in streams:
         with torch.cuda.stream(c):
             _ffi.check(_ffi.lib().cdetr_delay(1, _ffi.stream_ptr()), "cdetr_delay")
@@ -1773,7 +1769,6 @@ def streams_overlap(a, b):
     default --, and two streams of one queue never overlap: measured, not assumed.)  A 0.6 ms idle kernel on `a`, a 1 us kernel on `b` behind
     an event recorded on `a` BEFORE the idle kernel: 0.02 ms from that event to the end of b's kernel when they overlap, 0.61 when they
     do not (both streams warm, see warm_streams)."""
-    from . import _ffi
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(a):

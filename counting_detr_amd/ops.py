@@ -161,6 +161,10 @@ def splitk_ws():
     return t
 
 
+GEMM_A_GROUPS, GEMM_C_GROUPS, GEMM_PRIO, GEMM_RESID_GROUPS, GEMM_GATE16_ONLY = (
+    _ffi.DEFINES["GEMM_" + k] for k in ("A_GROUPS", "C_GROUPS", "PRIO", "RESID_GROUPS", "GATE16_ONLY"))       # cdetr_gemm_desc.flags
+
+
 def gemm_raw(A, lda, B, ldb, Cout, ldc, M, N, K, taps=1, b_layout=0, bias=None, w_scale=None, resid=None, ldr=0,
              gate=None, ldg=0, relu=False, out_scale=1.0, geom=None, batch=1, sA=0, sB=0, sC=0, B_split=None,
              batch_inner=0, sA2=0, sB2=0, sC2=0, precision=None, C16=None, A16=None, A16lo=None, C16lo=None, dl=None, probe_ws=None, B16=None, gate16=None,
@@ -169,15 +173,15 @@ def gemm_raw(A, lda, B, ldb, Cout, ldc, M, N, K, taps=1, b_layout=0, bias=None, 
     d = GemmDesc()
     d.C16, d.A16, d.A16lo, d.C16lo, d.B16, d.gate16 = ptr(C16), ptr(A16), ptr(A16lo), ptr(C16lo), ptr(B16), ptr(gate16)
     if A_split is not None:        # interleaved groups [hi 32 | lo 32] travel in the A16 / C16lo fields under a flag (include/cdetr_hip.h)
-        d.A16, d.flags = ptr(A_split), d.flags | 1
+        d.A16, d.flags = ptr(A_split), d.flags | GEMM_A_GROUPS
     if C_split is not None:
-        d.C16lo, d.flags = ptr(C_split), d.flags | 2
+        d.C16lo, d.flags = ptr(C_split), d.flags | GEMM_C_GROUPS
     if prio:
-        d.flags |= 4                # CDETR_GEMM_PRIO
+        d.flags |= GEMM_PRIO
     if resid_groups:
-        d.flags |= 8                # CDETR_GEMM_RESID_GROUPS: `resid` is an interleaved-groups tensor
+        d.flags |= GEMM_RESID_GROUPS        # `resid` is an interleaved-groups tensor
     if gate16_only:
-        d.flags |= 16               # CDETR_GEMM_GATE16_ONLY: `gate` is no fp32 tensor, only its twin may be read
+        d.flags |= GEMM_GATE16_ONLY         # `gate` is no fp32 tensor, only its twin may be read
     d.batch_inner, d.sA2, d.sB2, d.sC2 = batch_inner, sA2, sB2, sC2
     d.M, d.N, d.K, d.taps, d.batch, d.b_layout, d.relu, d.out_scale = M, N, K, taps, batch, b_layout, int(relu), out_scale
     d.precision = PRECISION if precision is None else precision
@@ -2415,7 +2419,6 @@ def nms_suppress(prob, boxes, orig_hw, threshold, iou, out=None, removed=None, e
     suppressed entries NaN, every other entry bit for bit; removed int32 [B]).  `out` / `removed`: tensors to write into (out must not be
     prob).  One launch on the current stream, nothing comes back to the host; Q > 4096 raises before any launch.  events: a pair of
     torch.cuda.Event recorded right before / after the launch (tools/nms_time.py)."""
-    from ._ffi import nms_suppress_desc
     from .nms import check_iou
     from .threshold_sweep import widen
     _expect("nms_suppress", torch.float32, prob=prob, boxes=boxes, out=out)
@@ -2433,7 +2436,7 @@ def nms_suppress(prob, boxes, orig_hw, threshold, iou, out=None, removed=None, e
     B, Q = prob.shape
     out = torch.empty_like(prob) if out is None else out
     removed = torch.empty(B, dtype=torch.int32, device=prob.device) if removed is None else removed
-    d = nms_suppress_desc()
+    d = _ffi.NmsSuppressDesc()
     d.B, d.Q, d.threshold, d.iou = B, Q, widen(threshold), check_iou(iou)
     d.prob, d.boxes, d.orig_hw, d.prob_out, d.removed = ptr(prob), ptr(boxes), ptr(orig_hw), ptr(out), ptr(removed)
     with _between(events):

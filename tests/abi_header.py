@@ -1,5 +1,6 @@
-"""include/cdetr_hip.h as the ABI tests read it: the fields of a descriptor struct in declaration order, and the header name of a ctypes twin
-of counting_detr_amd/_ffi.py.  Not a test module; imported by tests/test_abi.py and the per-feature CPU tests."""
+"""include/cdetr_hip.h as the ABI tests read it: the fields of a descriptor struct in declaration order, the prototypes, and the header name of a
+ctypes twin of counting_detr_amd/_ffi.py.  The tests' OWN reader: _ffi derives its binding from the same header, so nothing here may come from
+the package.  Not a test module; imported by tests/test_abi.py and the per-feature CPU tests."""
 import os
 import re
 
@@ -27,6 +28,31 @@ def struct_fields(struct_name):
         for i, nm in enumerate(decl.split(",")):
             out.append((re.findall(r"(\w+)\s*$", nm.strip())[0], base, "*" in (decl.split(",")[0] if i == 0 else nm)))
     return out
+
+
+def struct_names():
+    """Every `typedef struct { ... } name;` of the header, in declaration order."""
+    return re.findall(r"typedef struct \{[^}]*\}\s*(\w+)\s*;", re.sub(r"/\*.*?\*/", "", source(), flags=re.S))
+
+
+def prototypes():
+    """[(function name, return type, [(C base type without const, is a pointer), ...])] in declaration order; `static inline` helpers are
+    no part of the ABI and are left out."""
+    src = re.sub(r"/\*.*?\*/", "", source(), flags=re.S)
+    out = []
+    for ret, name, params in re.findall(r"^\s*(int|size_t|const char\*)\s+(cdetr_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            base, star = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*\w+\s*", p).groups()
+            args.append((base, star == "*"))
+        out.append((name, ret, args))
+    return out
+
+
+def function_names():
+    """Every declared function, sorted: read more loosely than prototypes(), so a prototype that one cannot parse is still counted."""
+    src = re.sub(r"/\*.*?\*/", "", source(), flags=re.S)
+    return sorted(set(re.findall(r"^\s*(?:int|size_t|const char\*)\s+(cdetr_\w+)\s*\(", src, flags=re.M)))
 
 
 def field_names(struct_name):
