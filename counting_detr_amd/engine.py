@@ -10,6 +10,8 @@ A2/infer.py:27-122, re-designed for one-process-per-GPU data parallelism on MI35
     segment is final and overlapped with the remaining backbone backward;
   * the step issues no host sync (device matcher, device loss normaliser), so it can be captured in a HIP graph.
 """
+import contextlib
+import gc
 import math
 import os
 import sys
@@ -19,6 +21,7 @@ import torch.distributed as dist
 
 from . import _ffi
 from . import backbone as _bb
+from .frozen_stage import FrozenStages, batch_token, capture_frozen_stage
 from .misc import NestedTensor, get_world_size, is_dist_avail_and_initialized, nested_tensor_from_tensor_list, reduce_dict
 
 UNUSED_PREFIXES = ("input_proj.",)   # built but never used on the stage-2 path: grad stays None in the reference
@@ -305,6 +308,30 @@ def _scoped(fn):
     return wrapper
 
 
+@contextlib.contextmanager
+def _no_gc():
+    """Python's cyclic garbage collector stays off while an engine captures graphs (a `with` block or a decorator).  A collection that starts inside a
+    capture destroys whatever garbage it finds there and then -- on the capturing thread or on autograd's -- and twice that ended the process
+    (SIGABRT with the collector as the innermost frame: once under a captured forward, once under a captured backward).  torch.cuda.graph no
+    longer collects ahead of a capture either; garbage waits until the capture is over."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
+
+
+def _weakly(method):
+    """A bound method as a callable that does not keep its object alive.  An engine hands its own capture method to the FrozenStages it owns: held
+    strongly, that is a reference cycle, and the engine -- with every graph and graph-pool buffer it owns -- would be destroyed by a garbage
+    collection at some later time (inside another engine's capture: the process aborts) instead of at the moment it is dropped."""
+    import weakref
+    ref = weakref.WeakMethod(method)
+    return lambda *a: ref()(*a)
+
+
 def model_unused_prefixes(model):
     """Parameter-name prefixes the model's configuration leaves out of the loss (the transformer's `unused_prefixes`, e.g. adapt_pos1d for
     attention_type "nn.MultiheadAttention"), as full names."""
@@ -386,26 +413,20 @@ class Trainer:
         self._cache = {}                        # step(): captured steps by (image shape, exemplar shape, target capacity, arithmetic), LRU order
         self._pool = None                       # ONE graph memory pool for every cached step (entries never run concurrently)
         self._prefetch_on = bool(getattr(args, "frozen_prefetch", True)) and os.environ.get("CDETR_FROZEN_PREFETCH", "1") != "0"
-        self._pf_timeout_us = int(os.environ.get("CDETR_PF_TIMEOUT_US", getattr(args, "frozen_prefetch_timeout_us", 400)))   # flag wait (chain layout)
+        # the prefetch stream's flag wait (chain layout) gives up after this long: it reaches the wait as soon as Z is done (~1.9 ms into the step)
+        self._pf_timeout_us = int(os.environ.get("CDETR_PF_TIMEOUT_US", getattr(args, "frozen_prefetch_timeout_us", 4000)))
         self._captured_allreduce = os.environ.get("CDETR_CAPTURED_ALLREDUCE", "1" if getattr(args, "captured_allreduce", False) else "0") == "1"
         self._z_late = os.environ.get("CDETR_Z_LATE", "1") != "0"               # Z released by the backbone-forward-done signal instead of at step start
         self._z_timeout_us = int(os.environ.get("CDETR_Z_TIMEOUT_US", 4000))    # its flag wait gives up after this long (a lost signal = a delay, never a hang)
         self._pf_post_us = int(os.environ.get("CDETR_PF_POST_US", 30))          # head start of the solve over the prefetched stage's workgroups
-        self._pf_delay_us = int(os.environ.get("CDETR_PF_DELAY_US", 0))        # "single" layout only: fixed delay in front of the prefetched stage
-        self._pf_eager = os.environ.get("CDETR_PF_EAGER", "0") == "1"
-        self._fs_stage_x = os.environ.get("CDETR_FS_STAGE_X", "1") != "0"      # the frozen stage's fp32 output through a staging buffer (no event between F and B)
-        if self._fs_stage_x and "CDETR_PF_TIMEOUT_US" not in os.environ and not hasattr(args, "frozen_prefetch_timeout_us"):
-            self._pf_timeout_us = 4000        # the prefetch stream reaches its flag wait as soon as Z is done (~1.9 ms into the step), not at the forward's end
-        self._fs_copy_on_side = int(os.environ.get("CDETR_FS_COPY_ON_SIDE", "0"))      # xs -> x on the side stream behind W0 instead of at the next step's head
         self._fs_twin_on_side = os.environ.get("CDETR_FS_TWIN_ON_SIDE", "1") == "1"      # x16s -> x16 on the prefetch stream beside the forward instead of at the step's head
-        self._b_first = os.environ.get("CDETR_B_FIRST", "0") == "1"           # A/B: submit B before the prefetch stream's flag wait (see _run_entry: it loses)
         # workgroups of the in-line tail launch (0 = the library's default, 384): 8.82 / 8.73 / 8.70 / 8.67 ms at 384 / 768 / 2048 / 4096, flat to
         # 8192, +0.04 at 16384 (profiles/r5_ab_tail_wgrad.txt)
         self._tail_wg_target = int(os.environ.get("CDETR_TAIL_WG_TARGET", "6144"))
         self._zero_arena_on = os.environ.get("CDETR_ZERO_ARENA", "1") != "0"      # A/B: 0 = the backward's accumulators are torch.zeros inside B
         self._arena_bufs = []                      # ops.ZeroArena buffers of the cached steps (shared by every step they are large enough for)
         self._tail_inline = float(os.environ.get("CDETR_TAIL_INLINE", getattr(args, "wgrad_tail_inline", 1.0)))   # share of layer2's weight gradients kept on the main stream
-        self._frozen = {}                       # image shape -> frozen-stage buffers + graph (see "frozen-stage prefetch")
+        self._frozen = FrozenStages(_weakly(self._capture_frozen))      # image shape -> frozen-stage buffers + graph (see "frozen-stage prefetch")
         self._pf_stream = self._pf_pool = self._wg_stream = None
         self._serial = False                    # _side_streams(): no stream runs beside the main one -> no prefetch, no flag waits
         self._inject = {}                       # tests: {"before_B": us, "before_Z": us, "before_W0": us} idle kernels at those points of a chain step
@@ -899,38 +920,33 @@ class Trainer:
         e = self._cache.pop(key)
         self._release_frozen(e)
 
+    def _stages_in_use(self, but=None):
+        """The frozen stages that captured steps read (every step but `but`)."""
+        return [x["fs"] for x in list(self._cache.values()) + [self._entry] if x is not None and x is not but and x.get("fs") is not None]
+
     def _release_frozen(self, e):
-        fs = e.get("fs") if e is not None else None
-        if fs is None:
-            return
-        live = [x for x in list(self._cache.values()) + [self._entry] if x is not None and x is not e and x.get("fs") is fs]
-        if not live:
-            for shape, f in list(self._frozen.items()):
-                if f is fs:
-                    del self._frozen[shape]
+        self._frozen.release(e.get("fs") if e is not None else None, self._stages_in_use(but=e))
 
     def _trim_frozen(self, limit=2):
         """Frozen-stage graphs that no captured step uses (a batch was announced and never arrived): keep the newest `limit`."""
-        used = {id(x["fs"]) for x in list(self._cache.values()) + [self._entry] if x is not None and x.get("fs") is not None}
-        idle = [shape for shape, f in self._frozen.items() if id(f) not in used]
-        for shape in idle[:max(0, len(idle) - limit)]:
-            torch.cuda.synchronize()
-            del self._frozen[shape]
+        self._frozen.trim(self._stages_in_use(), limit)
 
     # ------------------------------------------------------------------ frozen-stage prefetch
     # The stem + layer1 (A2/models/backbone.py:93-95: frozen, and the images need no gradient) of batch i+1 depends on nothing step i
     # updates.  It is an HBM-bound 0.6 ms at two 800x800 images; the step has a window where the chip is all but idle (the Hungarian
-    # solve: one wavefront per image for ~0.3 ms, then the latency-bound decoder / encoder backward).  So a captured step is TWO graphs,
-    # [forward] | [matcher + criterion + backward (+ optimizer)], and between their launches the frozen stage of the NEXT batch -- its own
-    # small graph per image shape, on its own stream, with its own graph memory pool and split-reduction scratch -- is released behind an
-    # event: it runs beside the solve.  Its fp32 output goes straight into the buffer the next forward reads (this step's forward is done
-    # with it; the backward reads the bf16 twin only), the twin into a staging copy that the next step moves over (41 MB, ~15 us).
+    # solve: one wavefront per image for ~0.3 ms, then the latency-bound decoder / encoder backward).  So between the launches of a captured
+    # step's forward and of its solve, the frozen stage of the NEXT batch -- its own small graph per image shape (frozen_stage.FrozenStage),
+    # on the prefetch stream, with its own graph memory pool and split-reduction scratch -- is released: it runs beside the solve.
+    # The stage writes only its own buffers: it reads `images` and writes the staging buffers `xs` (fp32) and `x16s` (the bf16 twin).  The
+    # head of the step that consumes it moves xs -> x, the buffer its forward reads (~35 us); the twin, which only the backward reads, moves
+    # x16s -> x16 on the prefetch stream beside that forward (41 MB; CDETR_FS_TWIN_ON_SIDE=0: at the step's head as well).  A stage running
+    # ahead therefore never writes what a running forward or backward reads, and no event ties it to either (_run_entry).
     # A batch that was not announced (first step, another object than the announced one) runs its frozen stage in line, as before.
     def _prefetch_ok(self):
         """The next batch's frozen stage may run beside this step only if (a) a side stream really runs beside the main one (probed), and
-        (b) the backward of this step reads layer1's output through its bf16 TWIN only -- the prefetch overwrites the fp32 tensor while the
-        backward is still running, and the weight gradients of layer2[0] (conv1, downsample) read X = that tensor: with a backward arithmetic
-        that does not feed on twins they would read it as fp32."""
+        (b) the backward of this step reads layer1's output through its bf16 TWIN -- every stage is captured with one and the captured forward
+        hands (x, x16) to the trunk: with a backward arithmetic that does not feed on twins the weight gradients of layer2[0] (conv1,
+        downsample) read X as fp32 and the stream-ordered forward builds no twin, so such a step runs its frozen stage inside its forward."""
         from . import ops
         if not (self._prefetch_on and self.flat_g.is_cuda):
             return False
@@ -940,80 +956,40 @@ class Trainer:
 
     def _frozen_for(self, shape):
         """Static buffers + captured graph of the frozen stage for one padded image shape."""
-        from . import ops
-        shape = tuple(shape)
-        fs = self._frozen.pop(shape, None)
-        if fs is not None:
-            self._frozen[shape] = fs               # most recently announced / used last: _trim_frozen keeps the NEWEST idle entries
-            return fs
-        _ = self.mirror                            # (re)built outside the capture below
-        body = self.model.backbone.body
-        B, _, H, W = shape
-        h, w = body.frozen_out_hw(H, W)
-        dev = self.device
-        fs = {"images": torch.zeros(shape, device=dev), "x": torch.empty((B, h, w, 256), device=dev),
-              "x16": torch.empty((B, h, w, 256), device=dev, dtype=torch.bfloat16),
-              "x16s": torch.empty((B, h, w, 256), device=dev, dtype=torch.bfloat16), "token": None, "keep": None}
-        # Round 6: the fp32 output is staged like the twin (the stage writes `xs`, the step's head copies xs -> x), so the prefetched stage never
-        # writes what a running forward reads and needs NO event between the forward graph and the solve's graph: that event's marker cost the
-        # main queue ~0.09 ms per step (the graph launched behind it started 30-160 us late; profiles/r6_step_gaps.txt); the copy costs ~35 us
-        fs["xs"] = torch.empty((B, h, w, 256), device=dev) if self._fs_stage_x else fs["x"]
-        # (a HIP CU-masked stream -- hipExtStreamCreateWithCUMask, leaving 16-64 CUs to the step's own latency-bound chain -- was tried:
-        # with such a queue alive EVERY launch of the process slowed down, 9.3 -> 19 ms per step, in-line replays included:
-        # profiles/r4_prefetch_ab_cumask.txt; an ordinary stream it is)
-        ps, _ = self._side_streams()
-        with ops.scope(MIRROR=self.mirror, BRANCH_BESIDE=0):      # a LINEAR graph: every node runs on the stream it is launched on
-            if self.mirror is not None:
-                self.mirror.refresh("fwd")                      # the frozen layers' pre-split images (rewritten, unchanged, by every step)
-            ps.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(ps):
-                body.frozen_stage(fs["images"], True, out_to=(fs["xs"], fs["x16s"]))       # lazily cached tables exist before the capture
-            torch.cuda.current_stream().wait_stream(ps)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            mode = {"capture_error_mode": "thread_local"} if get_world_size() > 1 else {}
-            with torch.cuda.graph(g, pool=self._pf_pool, stream=ps, **mode):
-                body.frozen_stage(fs["images"], True, out_to=(fs["xs"], fs["x16s"]))
-        fs["graph"] = g
-        self._frozen[shape] = fs
-        self._trim_frozen()
+        new = shape not in self._frozen
+        fs = self._frozen.for_shape(shape)         # (most recently announced / used last: _trim_frozen keeps the NEWEST idle stages)
+        if new:
+            self._trim_frozen()
         return fs
 
-    @staticmethod
-    def _token(obj):
-        """Identity of a batch as the caller hands it over: the image tensor object itself ([B,3,H,W], or a NestedTensor's `.tensors`)
-        and its version counter -- an announced batch is recognised when the very same, unmodified tensor comes back.  None: a list of
-        images (padded into a fresh tensor on arrival) cannot be announced."""
-        t = obj.tensors if hasattr(obj, "tensors") else obj
-        if not torch.is_tensor(t) or t.dim() != 4 or not t.is_cuda:
-            return None
-        return (id(t), t._version, t.data_ptr())
+    @_no_gc()
+    def _capture_frozen(self, shape):
+        mirror = self.mirror                       # (re)built outside the capture
+        ps, _ = self._side_streams()
+        # the frozen layers' pre-split images (rewritten, unchanged, by every step) exist before the warm run
+        return capture_frozen_stage(self.model.backbone.body, shape, self.device, True, mirror, ps, self._pf_pool,
+                                    capture_error_mode="thread_local" if get_world_size() > 1 else None,
+                                    before_warm=(lambda: mirror.refresh("fwd")) if mirror is not None else None)
 
     def _frozen_ready(self, e, token):
-        """Make the frozen stage's output for the entry's current images available in fs['x'] / fs['x16'] (main stream)."""
+        """Make the frozen stage's output for the entry's current images available in fs.x / fs.x16 (main stream)."""
         fs = e["fs"]
         main = torch.cuda.current_stream()
         self._events().order(main, self._pf_stream)             # whatever was prefetched has landed
-        hit = not (token is None or fs["token"] != token)
-        if not hit:                                             # not announced (or another batch than the announced one): in line
-            fs["images"].copy_(e["st"]["images"])
-            fs["graph"].replay()
-            self.prefetch_stats["inline"] += 1
-        else:
+        if fs.claim(token):
             self.prefetch_stats["hits"] += 1
-        x_done = fs.get("x_done") is not None and fs.get("x_done") == token and hit
-        fs["token"] = fs["keep"] = fs["x_done"] = None
-        if self._fs_twin_on_side and e.get("layout") == "chain":
+        else:                                                   # not announced (or another batch than the announced one): in line
+            fs.run(e["st"]["images"])
+            self.prefetch_stats["inline"] += 1
+        twin_later = self._fs_twin_on_side and e.get("layout") == "chain"
+        if twin_later:
             e["twin_pending"] = fs       # only the backward reads the twin (layer2's weight gradients, behind Z's event): _run_entry copies it on the prefetch stream
-        else:
-            fs["x16"].copy_(fs["x16s"])
-        if fs["xs"] is not fs["x"] and not x_done:             # (x_done: the prefetch stream moved xs -> x itself at the end of the previous step)
-            fs["x"].copy_(fs["xs"])
+        fs.land(twin=not twin_later)
 
-    def _prefetch(self, images, token, keep, ordered=False):
+    def _prefetch(self, images, token, ordered=False):
         """Release the frozen stage of the announced next batch behind everything issued so far on the current stream (`ordered`: the
-        prefetch stream is already ordered behind it and has idled its delay)."""
-        fs = self._frozen.get(tuple(images.shape))
+        prefetch stream is already ordered behind it)."""
+        fs = self._frozen.get(images.shape)
         if fs is None:                      # (resolved before the step's first launch by _replay_entry; a shape met here for the first time is
             return                          # not worth a capture in the middle of a step: that batch runs its frozen stage in line)
         ps = self._pf_stream
@@ -1022,17 +998,9 @@ class Trainer:
             ev.record(torch.cuda.current_stream())
             ps.wait_event(ev)
         with torch.cuda.stream(ps):
-            fs["images"].copy_(images, non_blocking=True)
-            if self._pf_delay_us > 0 and not ordered:     # the solve first (it needs a whole CU's LDS), the flood of stem / layer1 workgroups after it
-                _ffi.check(_ffi.lib().cdetr_delay(self._pf_delay_us, _ffi.stream_ptr()), "cdetr_delay")
-            if self._pf_eager:                 # stream-ordered launches instead of the graph (A/B: CDETR_PF_EAGER)
-                from . import ops
-                with ops.scope(MIRROR=self.mirror, BRANCH_BESIDE=0):
-                    self.model.backbone.body.frozen_stage(fs["images"], True, out_to=(fs["xs"], fs["x16s"]))
-            else:
-                fs["graph"].replay()
-        fs["token"], fs["keep"] = token, keep                   # (`keep`: the announced object stays alive, so its id cannot be re-used)
+            fs.announce(images, token)
 
+    @_no_gc()
     def _capture_entry(self, images, mask, rects, targets, warmup=0):
         from . import ops
         _ = self.mirror                            # (re)built OUTSIDE any capture: its tables are uploaded with synchronous copies
@@ -1060,13 +1028,9 @@ class Trainer:
                 # (a prefetch of this very fs -- announced by the previous step, whose key differed only in capacity class / exemplar shape --
                 # may still be running on the prefetch stream: the same graph must not replay on two streams at once)
                 torch.cuda.current_stream().wait_stream(self._pf_stream)
-                fs["images"].copy_(st["images"])
-                fs["graph"].replay()
-                fs["x16"].copy_(fs["x16s"])
-                if fs["xs"] is not fs["x"]:
-                    fs["x"].copy_(fs["xs"])
-                fs["token"] = fs["keep"] = None
-                body.frozen_input = (fs["x"], fs["x16"])
+                fs.run(st["images"])
+                fs.land()
+                body.frozen_input = (fs.x, fs.x16)
             if layout == "chain":
                 e = self._capture_chain(st, world, warmup)
             else:
@@ -1350,7 +1314,7 @@ class Trainer:
         e["replays"] += 1
         announce = None
         if e["fs"] is not None and next_samples is not None:
-            tok = self._token(next_samples)
+            tok = batch_token(next_samples)
             if tok is not None:
                 announce = (next_samples.tensors if hasattr(next_samples, "tensors") else next_samples, tok)
                 # a shape announced for the first time: its frozen-stage graph is captured HERE, before anything of this step is launched
@@ -1381,7 +1345,7 @@ class Trainer:
             if e["g_p"] is not None:
                 e["g_p"].replay()
             if announce is not None:
-                self._prefetch(announce[0], announce[1], announce[0])
+                self._prefetch(*announce)
             e["g_a"].replay()
             if e["g_b"] is not None:
                 self.exchange.segment_done(0)          # everything above the backbone is final: first bucket leaves now
@@ -1401,7 +1365,7 @@ class Trainer:
         with torch.cuda.stream(pf):
             fsp = e.pop("twin_pending", None)
             if fsp is not None:                        # the frozen stage's bf16 twin moves into place beside the forward (41 MB; 23 us less at the step's head)
-                fsp["x16"].copy_(fsp["x16s"])
+                fsp.x16.copy_(fsp.x16s)
             idle("before_Z")
             if e.get("z_late"):                        # (zero-fill + weight images are floods: beside the latency-bound encoder / decoder, not the backbone)
                 _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr() + 8, self._sig.data_ptr() + 12, self._z_timeout_us, 0, _ffi.stream_ptr()), "cdetr_flag_wait")
@@ -1414,46 +1378,28 @@ class Trainer:
                 # A wait with timeout 0 advances `consumed` by exactly one, whichever side of the signal it lands on.
                 _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr(), self._sig.data_ptr() + 4, 0, 0, _ffi.stream_ptr()), "cdetr_flag_wait")
         e["F"].replay()
-
-        def release_prefetch():
-            # the next batch's frozen stage: behind F (event) AND behind the signal kernel that opens B -- the solve keeps its cost matrix in
-            # LDS (a whole compute unit's worth) and must be resident before the stem / layer1 workgroups take every CU
+        if announce is not None:
+            # The next batch's frozen stage, released by the signal kernel that opens B: the solve keeps its cost matrix in LDS (a whole compute
+            # unit's worth) and must be resident before the stem / layer1 workgroups take every CU.  It is submitted BEFORE B (submitted after
+            # it, the stage starts only when B has finished) and behind NO event on F (such an event's marker made B start 30-160 us late):
+            # both measured, profiles/r6_step_gaps.txt.
+            # INVARIANT: nothing but this flag wait orders the prefetched stage against the forward that is running -- a wait that times out
+            # lets the stage run beside F.  That is safe because the stage touches no buffer the forward reads: it writes its own `images`,
+            # `xs` and `x16s` (this step's head moved xs -> x on the main stream, ahead of the event above that opens the prefetch stream's part
+            # of the step; x16s -> x16 moved on the prefetch stream itself, ahead of the stage in stream order); and the frozen layers' forward
+            # weight images, which the stage reads while F's mirror.refresh("fwd") rewrites them, are rewritten with identical bytes.
             with torch.cuda.stream(pf):
                 _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr(), self._sig.data_ptr() + 4, self._pf_timeout_us, self._pf_post_us, _ffi.stream_ptr()),
                            "cdetr_flag_wait")
-            self._prefetch(announce[0], announce[1], announce[0], ordered=True)
-        if announce is not None:
-            if not self._fs_stage_x:      # (staged output: the stage writes nothing a running forward reads; ev0 + stream order cover the staging buffers)
-                evf = evs_.record(main)
-                evs_.wait(pf, evf)      # issued HERE in both orders: the wait makes the runtime submit the event's marker now -- left pending, the
-            if not self._b_first:       # marker completes with the batch of commands that follows it (B: measured, the frozen stage then started 2.3 ms late)
-                release_prefetch()
+            self._prefetch(*announce, ordered=True)
         evs_.wait(main, evz)
         idle("before_B")
         e["B"].replay()
-        if announce is not None and self._b_first:
-            # CDETR_B_FIRST=1 (round 6 A/B, off): B SUBMITTED before the prefetch stream's flag wait + frozen-stage graph (same device-side ordering:
-            # the event and the flag carry it).  tools/step_gaps.py shows the main queue idle for 75 us between F's last kernel and B's first and for
-            # another 55 us in front of the solve in pipelined steps (8 us / 0 in line).  Submitting B first removes both (the solve then runs 262 us
-            # instead of 326-364) -- but whatever is submitted to the prefetch stream AFTER B's launch does not start before B has finished: the frozen
-            # stage lands 2.3 ms late, under the backbone's backward (a 200 us hole there), and the step is 0.02-0.05 ms slower.  profiles/r6_step_gaps.txt
-            release_prefetch()
-        def stage_into_place():
-            # (CDETR_FS_COPY_ON_SIDE, A/B) the staged fp32 output of the NEXT batch's frozen stage moves into place on the side stream: behind the stage
-            # (stream order) and behind B (W0 waits for it: this step's forward is done with `x`) -- the next step's head then copies nothing.
-            # 1 = right behind W0 (beside the backbone's data gradients), 2 = behind the last weight-gradient graph (beside the tail of layer2's)
-            if announce is not None and self._fs_stage_x and wg is pf:
-                fsn = self._frozen.get(tuple(announce[0].shape))
-                if fsn is not None and fsn["token"] == announce[1] and fsn["xs"] is not fsn["x"]:
-                    fsn["x"].copy_(fsn["xs"])
-                    fsn["x_done"] = announce[1]
         if e["W0"] is not None:                        # the parameter gradients above the backbone: beside the backbone's data-gradient chain
             evs_.wait(wg, evs_.record(main))
             with torch.cuda.stream(wg):
                 idle("before_W0")
                 e["W0"].replay()
-                if self._fs_copy_on_side == 1:
-                    stage_into_place()
         if dp:
             self.exchange.segment_done(0, also=wg if e["W0"] is not None else None)      # first bucket: everything above the backbone
         tr_ = self.exchange.trace
@@ -1473,9 +1419,6 @@ class Trainer:
             if dp:
                 for seg in segs:
                     self.exchange.segment_done(seg, also=wg if gw is not None else None)
-        if self._fs_copy_on_side == 2 and e["W0"] is not None:
-            with torch.cuda.stream(wg):
-                stage_into_place()
         evs_.order(main, wg)
         if dp:
             self.exchange.finish()
@@ -1495,7 +1438,7 @@ class Trainer:
             nt = samples if hasattr(samples, "decompose") else nested_tensor_from_tensor_list(samples)
             images, mask = nt.decompose()
             self._load_entry(e, images, mask, rects, targets)
-            token = self._token(samples)
+            token = batch_token(samples)
         elif pipelined and e["fs"] is not None:
             token = ("entry", id(e), e["loads"])
             e["replays"] += 1
@@ -1529,7 +1472,7 @@ class Trainer:
         images, mask = nt.decompose()
         key = self._cache_key(images, rects, targets)
         e = self._cache.pop(key, None)
-        token = self._token(samples)
+        token = batch_token(samples)
         if e is None:
             while len(self._cache) >= max(self._cache_size, 1):
                 torch.cuda.synchronize()           # nothing of the entry being dropped is still running
@@ -1832,7 +1775,7 @@ class InferenceEngine:
         self._stream = None
         self._pool = None                # one graph memory pool for all shapes (graphs never run concurrently; outputs stay allocated)
         self._prefetch_on = bool(prefetch) and os.environ.get("CDETR_FROZEN_PREFETCH", "1") != "0" and hasattr(model, "backbone")
-        self._frozen, self._pf_stream, self._pf_pool, self._sig = {}, None, None, None
+        self._frozen, self._pf_stream, self._pf_pool, self._sig = FrozenStages(_weakly(self._capture_frozen)), None, None, None
         self.stats = {"captures": 0, "calls": 0, "prefetch_hits": 0}
         import weakref
         model.__dict__.setdefault("_graph_cache_owners", []).append(weakref.ref(self))      # (riding too: a real invalidation reaches it)
@@ -1911,38 +1854,19 @@ class InferenceEngine:
         counts, keep, prob = count_from_logits(outputs["pred_logits"], self.threshold)
         return counts, keep, outputs, ref, prob
 
-    # ---- frozen-stage prefetch (see the class docstring; the training-side twin is Trainer._frozen_for / _prefetch)
+    # ---- frozen-stage prefetch (see the class docstring): the stages are frozen_stage.FrozenStage, as the trainer's, without the bf16 twin
     def _frozen_for(self, shape):
-        from . import ops
-        shape = tuple(shape)
-        fs = self._frozen.pop(shape, None)
-        if fs is not None:
-            self._frozen[shape] = fs               # most recently announced / used last: _trim_frozen keeps the NEWEST idle entries
-            return fs
-        _ = self.mirror                            # (re)built outside the capture below
-        body = self.model.backbone.body
-        B, _, H, W = shape
-        h, w = body.frozen_out_hw(H, W)
+        return self._frozen.for_shape(shape)
+
+    @_no_gc()
+    def _capture_frozen(self, shape):
+        mirror = self.mirror                       # (re)built outside the capture
         if self._pf_stream is None:
             self._pf_stream, _ = probe_side_stream(torch.cuda.current_stream(), self.device)
             self._sig = torch.zeros(2, dtype=torch.int32, device=self.device)
         if self._pf_pool is None:
             self._pf_pool = torch.cuda.graph_pool_handle()
-        ps = self._pf_stream
-        fs = {"images": torch.zeros(shape, device=self.device), "x": torch.empty((B, h, w, 256), device=self.device),
-              "xs": torch.empty((B, h, w, 256), device=self.device), "token": None, "keep": None}
-        with ops.scope(MIRROR=self.mirror, BRANCH_BESIDE=0):
-            ps.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(ps):
-                body.frozen_stage(fs["images"], False, out_to=(fs["xs"], None))
-            torch.cuda.current_stream().wait_stream(ps)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._pf_pool, stream=ps):
-                body.frozen_stage(fs["images"], False, out_to=(fs["xs"], None))
-        fs["graph"] = g
-        self._frozen[shape] = fs
-        return fs
+        return capture_frozen_stage(self.model.backbone.body, shape, self.device, False, mirror, self._pf_stream, self._pf_pool)
 
     @_scoped
     @torch.no_grad()
@@ -1970,15 +1894,13 @@ class InferenceEngine:
             after = None
             try:
                 if fs is not None:                     # the captured forward reads the frozen stage's output from a fixed buffer
-                    fs["images"].copy_(st[0])
-                    fs["graph"].replay()
-                    fs["x"].copy_(fs["xs"])
-                    fs["token"] = None
-                    body.frozen_input = (fs["x"], None)
+                    fs.run(st[0])
+                    fs.land()
+                    body.frozen_input = (fs.x, None)
                     sig = self._sig
                     after = lambda: _ffi.check(_ffi.lib().cdetr_flag_signal(sig.data_ptr(), _ffi.stream_ptr()), "cdetr_flag_signal")      # noqa: E731
                 # a LINEAR graph (no in-graph forks): hipGraphLaunch enqueues it in ~0.1 ms of host time (2.7 ms with forks)
-                with ops.scope(BRANCH_BESIDE=0, AFTER_BACKBONE=after):
+                with ops.scope(BRANCH_BESIDE=0, AFTER_BACKBONE=after), _no_gc():
                     self._run(*st)                     # lazily cached tables of this shape exist before the capture
                     if after is not None:              # (that run signalled too: keep `consumed` level with the counter)
                         with torch.cuda.stream(self._pf_stream):
@@ -2000,19 +1922,17 @@ class InferenceEngine:
             e[1][0].copy_(images)
             e[1][1].copy_(mask)
             e[1][2].copy_(rects)
-            token = Trainer._token(samples)
+            token = batch_token(samples)
         self._cache[key] = e
         if fs is not None:
             main = torch.cuda.current_stream()
             main.wait_stream(self._pf_stream)
-            if token is None or fs["token"] != token:
-                fs["images"].copy_(e[1][0])
-                fs["graph"].replay()
-            else:
+            if fs.claim(token):
                 self.stats["prefetch_hits"] += 1
-            fs["token"] = fs["keep"] = None
-            fs["x"].copy_(fs["xs"])                    # the forward reads x; the staging copy is free for the next batch's stage
-            tok = Trainer._token(next_samples) if next_samples is not None else None
+            else:
+                fs.run(e[1][0])
+            fs.land()                                  # the forward reads x; the staging copy is free for the next batch's stage
+            tok = batch_token(next_samples) if next_samples is not None else None
             if tok is not None:
                 nxt = next_samples.tensors if hasattr(next_samples, "tensors") else next_samples
                 f2 = self._frozen_for(nxt.shape)
@@ -2023,9 +1943,7 @@ class InferenceEngine:
                     # behind the copy above (event) and behind this call's backbone (signal kernel in the captured forward; the timeout only
                     # bounds how long a missing signal can hold the stage back)
                     _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr(), self._sig.data_ptr() + 4, 5000, 0, _ffi.stream_ptr()), "cdetr_flag_wait")
-                    f2["images"].copy_(nxt, non_blocking=True)
-                    f2["graph"].replay()
-                f2["token"], f2["keep"] = tok, nxt
+                    f2.announce(nxt, tok)
             elif self._sig is not None:
                 with torch.cuda.stream(self._pf_stream):      # the captured forward signals in every replay: consume the one nobody waits for
                     _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr(), self._sig.data_ptr() + 4, 0, 0, _ffi.stream_ptr()), "cdetr_flag_wait")

@@ -43,5 +43,5 @@ if e["layout"] == "chain":
 else:
     parts = [("g_f", e["g_f"]), ("g_p", e["g_p"]), ("g_a", e["g_a"])]
 if e["fs"] is not None:
-    parts.append(("frozen", e["fs"]["graph"]))
+    parts.append(("frozen", e["fs"].graph))
 print("host ms per launch: " + "  ".join(f"{n} {t(g.replay):.3f}" for n, g in parts if g is not None))
