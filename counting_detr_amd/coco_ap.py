@@ -47,6 +47,11 @@ printed and written.
 ERROR BREAKDOWN (`errors`, infer.py --error_report): WHY a detection failed -- duplicate, localisation, background, missed -- as one more reading of a
 `Matching`: counting_detr_amd/error_report.py states the rule in numpy (host flags), device flags go through ONE cdetr_coco_errors launch
 (csrc/error_report.hip) on the boxes where they lie: EQUAL codes, the IoUs bit for bit (tests/test_error_report_cpu.py, _gpu.py).
+
+BOOTSTRAP REPLICATES (`bootstrap`, infer.py --bootstrap R): HOW FAR the six numbers move when the images are resampled, as one more reading of a `Matching`:
+counting_detr_amd/bootstrap.py states the rule in numpy (host flags) -- every detection accumulated once with its image's multiplicity as weight, which EQUALS
+`accumulate` on the repeated lists --, device flags are packed where they lie by ONE cdetr_bootstrap_gather launch and the replicates run in cdetr_bootstrap_ap
+(csrc/bootstrap.hip), one copy back per launch: EQUAL numbers (tests/test_bootstrap_cpu.py, _gpu.py).
 """
 import json
 
@@ -329,6 +334,48 @@ class Matching:
                 dt_boxes, dt_area = dt_dev[0].reshape(-1), dt_dev[1]
             return ops.coco_errors(gt_boxes, gt_area, ig, i[:B + 1], dt_boxes, dt_area, i[B + 1:2 * B + 2], int(pack["g_max"]), er.IOU_FG, iou_bg,
                                    AREA_RNG["all"], dt_cnt=None if counts is None else i[2 * B + 2:], host=True)
+
+    def bootstrap(self, R, seed=0, counts=None, mult=None, chunk=None):
+        """-> float64 [R, 6]: AP, AP50, AP75, APs, APm, APl (x 100, NaN where undefined) of R bootstrap replicates over the images of
+        `image_ids` (counting_detr_amd/bootstrap.py states the rule; replicate r draws the same images as every other metric's replicate r),
+        of the first counts[k] detections of image k where `counts` is given.  Host flags: the numpy rule, slow.  Device flags: the merged order
+        goes up once, ONE cdetr_bootstrap_gather launch packs the flags where they lie and cdetr_bootstrap_ap (csrc/bootstrap.hip) runs the
+        replicates, one copy back per launch of `chunk` replicates: EQUAL numbers.  `mult`: int [R, N] multiplicities in place of the draws
+        (tests)."""
+        from . import bootstrap as bs
+        R, seed = bs.check_args(R, seed)
+        pack, N, A = self.pack, len(self.image_ids), len(self.areas)
+        if self.areas != tuple(AREA_RNG):
+            raise RuntimeError(f"coco_ap: the six numbers need a matching under {tuple(AREA_RNG)}, this one has {self.areas}")
+        slot = {int(i): k for k, i in enumerate(self.image_ids)}
+        if any(i not in slot for i in pack["image_ids"]):
+            raise RuntimeError("coco_ap: the pack holds images that `image_ids` does not name: the replicates draw from `image_ids`")
+        if N == 0:
+            return np.full((R, len(bs.AP_KEYS)), np.nan)
+        at = np.array([slot[i] for i in pack["image_ids"]], dtype=np.int64)
+        order, image = bs.prepare(pack["dt_score"], pack["dt_off"], self.pack_counts(counts))
+        image = at[image] if len(image) else image
+        if mult is not None:
+            mult = np.asarray(mult, dtype=np.int64).reshape(R, N)
+        if self.device is None:
+            matched, ignored, npig = self._host
+            npig_n = np.zeros((A, N), dtype=np.int64)
+            npig_n[:, at] = npig
+            m = bs.multiplicities(seed, R, N) if mult is None else mult
+            return bs.six_table(bs.ap_precisions(bs.flag_words(matched, ignored, order), image, npig_n, m), self.areas)
+        import torch
+        from . import ops
+        with torch.cuda.device(self.device):
+            i = torch.from_numpy(np.concatenate([order, image, at]).astype(np.int32)).to(self.device)
+            P, B = len(order), len(at)
+            npig_n = self.npig
+            if B != N or not np.array_equal(at, np.arange(N)):
+                npig_n = torch.zeros((A, N), dtype=torch.int32, device=self.device)
+                npig_n[:, i[2 * P:].long()] = self.npig
+            words = ops.bootstrap_gather(self.matched, self.det_ignored, i[:P])
+            rec = torch.from_numpy(REC_THRS).to(self.device)
+            dm = None if mult is None else torch.from_numpy(mult.astype(np.int32)).to(self.device)
+            return bs.six_table(ops.bootstrap_ap(words, i[P:2 * P], npig_n, rec, R, seed, mult=dm, chunk=chunk), self.areas)
 
     def row50(self):
         """-> (matched, det_ignored) [D] at area range `all`, IoU 0.5, row [0, 0] of the flags, for the renderer: views of the device tensors

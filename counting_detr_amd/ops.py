@@ -2097,6 +2097,103 @@ def coco_image_stats(matched, det_ignored, dt_off, npig, cuts, rec_thrs, dt_cnt=
     return tp.view(A, B, T, M), fp.view(A, B, T, M), ap.view(A, B, T)
 
 
+BOOTSTRAP_LAUNCH_BYTES = 64 << 20       # the replicates of one cdetr_bootstrap_ap launch: its precision table stays at or below this
+
+
+def _bootstrap_args(name, R, seed, N, mult, dev):
+    """The checks bootstrap_counts / bootstrap_ap share, made before anything is launched -> (R, seed, mult as a contiguous tensor or None)."""
+    from . import bootstrap as bs
+    R, seed = int(R), int(seed)
+    if N > bs.MAX_IMAGES or not 1 <= R <= bs.MAX_REPLICATES or not 0 <= seed < 2 ** 63:
+        raise RuntimeError(f"{name}: N = {N} images (limit {bs.MAX_IMAGES}), R = {R} replicates (1 .. {bs.MAX_REPLICATES}) or seed = {seed} "
+                           f"(0 .. 2^63 - 1) not supported")
+    if mult is not None:
+        _expect(name, torch.int32, mult=mult)
+        if tuple(mult.shape) != (R, N) or mult.device != dev:
+            raise RuntimeError(f"{name}: mult [R, N] = [{R}, {N}] on {dev} expected, got {tuple(mult.shape)} on {mult.device}")
+        mult = mult.contiguous()
+    return R, seed, mult
+
+
+def bootstrap_counts(gt, pred, R, seed, mult=None, host=False, events=None):
+    """cdetr_bootstrap_counts: the four sums behind MAE / RMSE / NAE / SRE for R bootstrap replicates over images in one launch
+    (counting_detr_amd/bootstrap.py: `count_sums` is the rule).  Device tensors: int32 gt [N], pred [N, Tc] (a view of rows with unit column
+    stride is read where it lies: ops.ThresholdSweep's table); `mult`: int32 [R, N] multiplicities used INSTEAD of the draws (tests).
+    -> S int64 [R, Tc, 2], F float64 [R, Tc, 2]: views of ONE buffer; host=True returns them as numpy arrays after a single copy."""
+    _expect("bootstrap_counts", torch.int32, gt=gt)
+    if pred.dtype != torch.int32 or gt.dim() != 1 or pred.dim() != 2 or pred.shape[0] != gt.shape[0] or gt.shape[0] < 1 or pred.device != gt.device \
+            or (pred.shape[0] > 1 and pred.stride(0) < pred.shape[1]) or pred.stride(1) != 1 or not gt.is_contiguous():
+        raise RuntimeError(f"bootstrap_counts: gt [N], pred [N, Tc] (unit column stride) on one device expected, got {tuple(gt.shape)}, "
+                           f"{tuple(pred.shape)} strides {pred.stride()}")
+    (N, Tc), dev = pred.shape, gt.device
+    if not 1 <= Tc <= 32:
+        raise RuntimeError(f"bootstrap_counts: Tc = {Tc} count columns, 1 .. 32 expected")
+    R, seed, mult = _bootstrap_args("bootstrap_counts", R, seed, N, mult, dev)
+    ld = pred.stride(0) if N > 1 else Tc
+    buf = torch.empty(2 * R * Tc * 2, dtype=torch.int64, device=dev)
+    S, F = buf[:R * Tc * 2], buf[R * Tc * 2:].view(torch.float64)
+    with _between(events):
+        check(lib().cdetr_bootstrap_counts(ptr(gt), ptr(pred), ld, ptr(mult), seed, 0, R, N, Tc, ptr(S), ptr(F), stream_ptr()), "cdetr_bootstrap_counts")
+    if host:
+        h = buf.cpu().numpy()
+        return h[:R * Tc * 2].reshape(R, Tc, 2), h[R * Tc * 2:].view("float64").reshape(R, Tc, 2)
+    return S.view(R, Tc, 2), F.view(R, Tc, 2)
+
+
+def bootstrap_gather(matched, det_ignored, order, events=None):
+    """cdetr_bootstrap_gather: coco_match's flags [A, T, D] (uint8, where they lie) and the merged order int32 [P] -> int32 [A, P] flag words."""
+    _expect("bootstrap_gather", torch.uint8, matched=matched, det_ignored=det_ignored)
+    _expect("bootstrap_gather", torch.int32, order=order)
+    if matched.dim() != 3 or matched.shape != det_ignored.shape or order.dim() != 1 or order.device != matched.device \
+            or det_ignored.device != matched.device:
+        raise RuntimeError(f"bootstrap_gather: flags [A, T, D] and order [P] on one device expected, got {tuple(matched.shape)}, "
+                           f"{tuple(det_ignored.shape)}, {tuple(order.shape)}")
+    (A, T, D), P = matched.shape, order.numel()
+    words = torch.empty((A, P), dtype=torch.int32, device=order.device)
+    with _between(events):
+        check(lib().cdetr_bootstrap_gather(ptr(matched) if D else None, ptr(det_ignored) if D else None, ptr(order) if P else None, A, T, D, P,
+                                           ptr(words) if P else None, stream_ptr()), "cdetr_bootstrap_gather")
+    return words
+
+
+def bootstrap_ap(words, image, npig, rec_thrs, R, seed, mult=None, chunk=None, events=None):
+    """cdetr_bootstrap_ap: the precision tables of R bootstrap replicates over images (counting_detr_amd/bootstrap.py: `ap_precision` is the
+    rule).  Device tensors: int32 words [A, P] (`bootstrap_gather`), image [P] (the image of every merged position, an index into the N
+    images the replicates draw from), npig [A, N]; float64 rec_thrs; `mult`: int32 [R, N] multiplicities used INSTEAD of the draws (tests).
+    -> precision float64 [R, A, 10, len(rec_thrs)] as a numpy array.  The replicates go in launches of `chunk` (default: as many as keep one
+    launch's table at or below BOOTSTRAP_LAUNCH_BYTES); ONE copy comes back per launch.  events: a LIST that receives one pair of
+    torch.cuda.Event per launch (tools/bootstrap_time.py)."""
+    import numpy as np
+    _expect("bootstrap_ap", torch.int32, words=words, image=image, npig=npig)
+    _expect("bootstrap_ap", torch.float64, rec_thrs=rec_thrs)
+    if words.dim() != 2 or npig.dim() != 2 or image.dim() != 1 or words.shape != (npig.shape[0], image.numel()) or npig.shape[1] < 1:
+        raise RuntimeError(f"bootstrap_ap: words [A, P], image [P], npig [A, N] expected, got {tuple(words.shape)}, {tuple(image.shape)}, "
+                           f"{tuple(npig.shape)}")
+    dev = npig.device
+    for name, t in (("words", words), ("image", image), ("rec_thrs", rec_thrs)):
+        if t.device != dev:
+            raise RuntimeError(f"bootstrap_ap: `{name}` on {t.device}, npig on {dev}")
+    (A, P), N, T, n_rec = words.shape, npig.shape[1], 10, rec_thrs.numel()
+    R, seed, mult = _bootstrap_args("bootstrap_ap", R, seed, N, mult, dev)
+    words, image, npig = words.contiguous(), image.contiguous(), npig.contiguous()
+    per = max(1, BOOTSTRAP_LAUNCH_BYTES // (A * T * n_rec * 8)) if chunk is None else int(chunk)
+    if per < 1:
+        raise RuntimeError(f"bootstrap_ap: chunk = {chunk} replicates per launch")
+    out = np.empty((R, A, T, n_rec))
+    for r0 in range(0, R, per):
+        n = min(per, R - r0)
+        table = torch.empty((n, A, T, n_rec), dtype=torch.float64, device=dev)
+        pair = None if events is None else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        with _between(pair):
+            check(lib().cdetr_bootstrap_ap(ptr(words) if P else None, ptr(image) if P else None, ptr(npig), None if mult is None else ptr(mult[r0:r0 + n]),
+                                           ptr(rec_thrs), seed, r0, n, N, P, A, T, n_rec, float(np.spacing(1)), ptr(table), stream_ptr()),
+                  "cdetr_bootstrap_ap")
+        if pair is not None:
+            events.append(pair)
+        out[r0:r0 + n] = table.cpu().numpy()
+    return out
+
+
 def coco_errors(gt_boxes, gt_area, gt_ignore, gt_off, dt_boxes, dt_area, dt_off, g_max, iou_fg, iou_bg, area_rng, dt_cnt=None, host=False,
                 events=None):
     """cdetr_coco_errors: the error breakdown of B packed images in one launch (counting_detr_amd/error_report.py states the rule).  Device

@@ -747,6 +747,51 @@ int cdetr_emit_detections(const cdetr_emit_detections_desc* d, void* stream);
 int cdetr_count_sweep(const float* prob, const float* thresholds, int32_t B, int32_t Q, int32_t T, int32_t* table, int32_t N, int32_t first,
                       void* stream);
 
+/* ---- bootstrap replicates over images (csrc/bootstrap.hip; infer.py / main.py --bootstrap R), which the reference does not have.
+ * counting_detr_amd/bootstrap.py states the rule in numpy; integers and FLOAT64 only, contraction into FMAs switched off, no atomics in
+ * global memory: every output EQUALS it bit for bit.  Replicate r of a split of N images has the multiplicities m[i] = #{j < N : draw(j) == i},
+ * all uint64 modulo 2^64:  x = (seed * 0x9E3779B97F4A7C15) ^ ((r << 32) | j);  x += 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ * x = (x ^ x >> 27) * 0x94D049BB133111EB;  x ^= x >> 31;  draw = ((x >> 32) * N) >> 32.  The workgroup that owns a replicate builds m in
+ * LDS (integer adds into LDS counters: order-free).  `mult` [R][N], when not NULL, is taken INSTEAD of the draws (row rb for replicate
+ * r0 + rb, every entry clamped into 0 .. 16384): hand-made weights for the tests.  The launch computes replicates r0 .. r0 + R - 1.
+ * Limits of all three: N <= 16384 images (m is 64 KB of LDS) and r0 + R <= 10000 replicates, CDETR_ERR_UNSUPPORTED beyond, naming the limit,
+ * before any launch; R == 0 launches nothing.
+ * cdetr_bootstrap_counts: one workgroup per replicate; for count column c (lane c of the first wave) with err_i = |gt[i] - pred[i][c]|, adding
+ *   in image order:  S [rb][c] = { sum m_i err_i, sum m_i err_i^2 } (int64),  F [rb][c] = { sum m_i * (err_i / gt_i), sum m_i * (err_i^2 / gt_i) }
+ *   (float64; one division and one product per term, no term where gt_i == 0).  pred is [N][ld] with Tc <= ld: the table cdetr_count_sweep
+ *   left on the device, or one uploaded column.  1 <= Tc <= 32.
+ * cdetr_bootstrap_gather: the flags of cdetr_coco_match [A][T][Dtot] -> words [A][P], position p = detection order[p] (the merged order,
+ *   computed once on the host): bit t = matched && !ignored at IoU threshold t, bit 16 + t = !matched && !ignored.  T == 10 exactly.  An
+ *   order entry outside 0 .. Dtot gives the word 0 and nothing is read.
+ * cdetr_bootstrap_ap: grid (replicate, area range), one wave per IoU threshold.  With w_p = m[image[p]] (0 for an image index outside
+ *   0 .. N), ctp_p / cfp_p the weighted inclusive prefix sums of the tp / fp bits and npig_r = sum_i m_i npig[a][i]:
+ *     precision [rb][a][t][s] = -1 when npig_r == 0; else the maximum of ctp_p / ((cfp_p + ctp_p) + eps) over the positions of weight > 0 with
+ *                              ctp_p / npig_r >= rec_thrs[s], 0 when there is none
+ *   = coco_ap._sample on the weighted list = coco_ap.accumulate on the list with every detection repeated m times.  Any P >= 0 (P == 0: the
+ *   pointers may be NULL; zeros, or -1); T == 10 exactly, n_rec <= 128.  Every element of `precision` is written exactly once.             */
+int cdetr_bootstrap_counts(const int32_t* gt,          /* [N] ground-truth counts */
+                           const int32_t* pred,        /* [N][ld] predicted counts, columns 0 .. Tc - 1 used */
+                           int32_t ld,
+                           const int32_t* mult,        /* [R][N] or NULL */
+                           int64_t seed, int32_t r0, int32_t R, int32_t N, int32_t Tc,
+                           int64_t* S,                 /* [R][Tc][2] */
+                           double* F,                  /* [R][Tc][2] */
+                           void* stream);
+int cdetr_bootstrap_gather(const uint8_t* matched, const uint8_t* det_ignored,   /* [A][T][Dtot], cdetr_coco_match's outputs, device */
+                           const int32_t* order,       /* [P] */
+                           int32_t A, int32_t T, int32_t Dtot, int32_t P,
+                           int32_t* words,             /* [A][P] */
+                           void* stream);
+int cdetr_bootstrap_ap(const int32_t* words,           /* [A][P], cdetr_bootstrap_gather's output */
+                       const int32_t* image,           /* [P] image of every position */
+                       const int32_t* npig,            /* [A][N] */
+                       const int32_t* mult,            /* [R][N] or NULL */
+                       const double* rec_thrs,         /* [n_rec] */
+                       int64_t seed, int32_t r0, int32_t R, int32_t N, int32_t P, int32_t A, int32_t T, int32_t n_rec,
+                       double eps,                     /* numpy.spacing(1) */
+                       double* precision,              /* [R][A][T][n_rec] */
+                       void* stream);
+
 /* ---- greedy non-maximum suppression ahead of the emit (csrc/nms.hip; infer.py --nms_iou): a FILTER on prob, EQUAL to the host rule of
  * counting_detr_amd/nms.py; FMA contraction is switched off in this translation unit.
  * cdetr_nms_suppress: ONE launch per forwarded batch, one workgroup per image.  The candidates of image b are the queries with

@@ -63,9 +63,19 @@ reports read the same one matching.  With --device_detections ONE cdetr_coco_err
 the written predictions for the same kernel; `--ap_on_host` is the numpy rule.  Same bytes on every route; with --sweep_thresholds the report describes the
 run's own --threshold.  Without the flag nothing changes.
 
+`--bootstrap R` (1 .. 10000; `--bootstrap_seed S`, default 0, an error without it) says HOW FAR the numbers move when the split is resampled: R bootstrap
+replicates over images, the same draws for every metric (counting_detr_amd/bootstrap.py states the rule).  The metrics gain <K>_lo / <K>_hi, the 95 % interval,
+for MAE / RMSE / NAE / SRE and -- where instances_<split>.json is there -- AP / AP50 / AP75 / APs / APm / APl, and bootstrap_<split>.json appears beside the
+predictions file ({"split", "threshold", "replicates", "seed", "level", "metrics": {K: {"value", "lo", "hi", "se", "undefined"}}}; with --sweep_thresholds also
+"sweep": every threshold's counting intervals, their paired differences to --threshold and "best_vs_threshold"; AP at the run's threshold only).  With
+--device_detections the replicates read the split's one matching where its flags lie (cdetr_bootstrap_gather, cdetr_bootstrap_ap) and the sweep's count table
+where it lies (cdetr_bootstrap_counts); any other run on a GPU matches the written predictions there for the same kernels; `--ap_on_host` is the numpy rule,
+slow for AP.  Same bytes on every route.  Without the flag nothing changes.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --error_report
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --bootstrap 1000
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_worst 8
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report --render_ids 3,17
@@ -132,6 +142,53 @@ class ErrorReport:
                 json.dump(self.report, handle)
 
 
+class Bootstrap:
+    """--bootstrap R for one pass, beside ImageReport / ErrorReport and with their three routes: `replicates` and `seed` of the draws, `gt_json`
+    (the split's box ground truth, or None: counting intervals only), where the replicates run (`device`: a CUDA device = cdetr_bootstrap_counts
+    / cdetr_bootstrap_ap, or None = the numpy rule of counting_detr_amd/bootstrap.py) and, after the pass, `report` = bootstrap.report's dict
+    (None for a pass without images)."""
+
+    def __init__(self, replicates, seed=0, gt_json=None, device=None):
+        from counting_detr_amd.bootstrap import check_args
+        (self.replicates, self.seed), self.gt_json, self.device, self.split, self.report = check_args(replicates, seed), gt_json, device, None, None
+
+    def _device_sums(self, table):
+        """The counting sums on `device`: the [N, T] int32 `table` ops.ThresholdSweep left there is read where it lies, else the counts go up."""
+        def sums(gt, pred, R, seed, mult):
+            import numpy as np
+            from counting_detr_amd import ops
+            with torch.cuda.device(self.device):
+                p = table if table is not None else torch.from_numpy(np.ascontiguousarray(pred, dtype=np.int32)).to(self.device)
+                return ops.bootstrap_counts(torch.from_numpy(gt.astype(np.int32)).to(self.device), p, R, seed, host=True)
+        return sums if self.device is not None else None
+
+    def run(self, image_ids, gt_counts, pred_counts, threshold, matching=None, counts=None, six=None, sweep=None, table=None):
+        """The report of one pass -> the metrics' <K>_lo / <K>_hi keys.  The images in the order they were run: replicate r draws the same
+        images for every metric.  `matching` (a coco_ap.Matching under the four area ranges whose `image_ids` are these, or None: no AP),
+        `counts` its prefix lengths and `six` the run's own six numbers (None: `matching.six()`); `sweep` (a threshold_sweep.Sweep after its pass:
+        counts [N, T] and report): the counting intervals of every threshold and their paired differences to `threshold`; `table`: the sweep's
+        counts as the device tensor they were formed in."""
+        import numpy as np
+        from counting_detr_amd import bootstrap as bs
+        from counting_detr_amd import threshold_sweep as ts
+        R, seed, N = self.replicates, self.seed, len(gt_counts)
+        pred, col = (np.asarray(pred_counts).reshape(N, 1), 0) if sweep is None else (np.asarray(sweep.counts).reshape(N, -1), ts.column(sweep.thresholds, threshold))
+        values, reps = bs.counting(gt_counts, pred, R, seed, self._device_sums(table[:N] if table is not None and sweep is not None else None))
+        section = bs.sweep_section(sweep.thresholds, threshold, values, reps, sweep.report["best"]) if sweep is not None else None
+        values, reps = {K: values[K][col] for K in bs.COUNT_KEYS}, {K: reps[K][:, col] for K in bs.COUNT_KEYS}
+        if matching is not None:
+            six, table6 = matching.six() if six is None else six, matching.bootstrap(R, seed, counts)
+            values.update({K: six[K] for K in bs.AP_KEYS})
+            reps.update({K: table6[:, k] for k, K in enumerate(bs.AP_KEYS)})
+        self.report = bs.report(self.split, threshold, R, seed, values, reps, section)
+        return bs.metrics(self.report)
+
+    def write(self, output_dir):
+        if self.report is not None:
+            with open(os.path.join(output_dir, "bootstrap_" + self.split + ".json"), "w") as handle:
+                json.dump(self.report, handle)
+
+
 class Render:
     """--render_worst K / --render_ids for one pass: the overlays of the images `render.select` picks from the pass's image report, written to
     render_<split>/ wherever the predictions file is (counting_detr_amd/render.py states the drawing rule).  `out_dir`: where the last pass
@@ -166,7 +223,8 @@ class Render:
 
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
-          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None, error_report=None):
+          per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None, error_report=None,
+          bootstrap=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -193,7 +251,10 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     `error_report` (an ErrorReport; None: off, and nothing changes): the metrics gain err_dup / err_loc / err_bkg / err_misloc / err_missed and the
     four dAP50_* numbers, and error_report_<split>.json is written wherever the predictions file is.  It reads the SAME one matching as
     `image_report` -- with `device_detections` and `gt_json` the store's (one cdetr_coco_errors launch on the boxes where they lie), otherwise
-    one of the predictions as written -- and does not need an image report."""
+    one of the predictions as written -- and does not need an image report.
+    `bootstrap` (a Bootstrap; None: off, and nothing changes): the metrics gain <K>_lo / <K>_hi for MAE / RMSE / NAE / SRE and, where
+    `bootstrap.gt_json` is set, for the six AP numbers, and bootstrap_<split>.json is written wherever the predictions file is.  The AP
+    replicates read the SAME one matching as the reports (with `device_detections` and `gt_json` the store's, its flags where they lie)."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
     if nms_iou is not None:
@@ -209,6 +270,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         image_report.split, image_report.report = split, None
     if error_report is not None:
         error_report.split, error_report.report = split, None
+    if bootstrap is not None:
+        bootstrap.split, bootstrap.report = split, None
     output_path = os.path.join(output_dir, "predictions_" + split + ".json") if write_json else None
     if output_path is not None and os.path.isfile(output_path):
         os.remove(output_path)
@@ -223,12 +286,14 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
         out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report,
-                            render, output_dir, nms_iou, error_report)
+                            render, output_dir, nms_iou, error_report, bootstrap)
         _write_sweep(sweep, output_dir, split)
         if image_report is not None and output_path is not None:
             image_report.write(output_dir)
         if error_report is not None and output_path is not None:
             error_report.write(output_dir)
+        if bootstrap is not None and output_path is not None:
+            bootstrap.write(output_dir)
         return out
     predictions = {"categories": [{"name": "fg", "id": 1}], "images": [], "annotations": []}
     anno_id = 1
@@ -313,6 +378,8 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         sweep.counts = np.concatenate(tables)
         sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows)
     _write_sweep(sweep, output_dir, split)
+    boot_ap = bootstrap is not None and bootstrap.gt_json is not None and n_img
+    matching = None
     if image_report is not None and n_img:
         matching = match_predictions(predictions, image_report.gt_json, image_ids, image_report.device)       # once, for the reports and the overlays
         metrics.update(image_report.from_matching(matching, None, image_ids, gt_counts, pred_counts, threshold))
@@ -321,11 +388,19 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
             if render is not None:
                 render.from_matching(matching, None, image_report, output_dir, threshold)
     if error_report is not None and n_img:
-        if image_report is None:                # no statistics asked for: the breakdown reads the boxes, one area range carries them
-            matching = match_predictions(predictions, error_report.gt_json, image_ids, error_report.device, ("all",))
+        if image_report is None:                # no statistics asked for: the breakdown reads the boxes, one area range carries them (the replicates need four)
+            matching = match_predictions(predictions, error_report.gt_json, image_ids, error_report.device, *(() if boot_ap else (("all",),)))
         metrics.update(error_report.from_matching(matching, None, image_ids, threshold))
         if output_path is not None:
             error_report.write(output_dir)
+    if bootstrap is not None and n_img:
+        if boot_ap and matching is None:
+            matching = match_predictions(predictions, bootstrap.gt_json, image_ids, bootstrap.device)
+        if boot_ap:
+            matching.image_ids = image_ids      # the images the replicates draw from, in the order they were run
+        metrics.update(bootstrap.run(image_ids, gt_counts, pred_counts, threshold, matching if boot_ap else None, sweep=sweep))
+        if output_path is not None:
+            bootstrap.write(output_dir)
     return metrics, predictions
 
 
@@ -347,7 +422,7 @@ def _num_images(data_loader):
 
 
 def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None,
-                  render=None, output_dir=None, nms_iou=None, error_report=None):
+                  render=None, output_dir=None, nms_iou=None, error_report=None, bootstrap=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -459,19 +534,25 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             sweep.report = ts.report(sweep.thresholds, sweep.counts, gt_counts, ap_rows if sweep.gt_json is not None else None)
         if matching is not None and gt_json is not None:
             metrics.update(matching.six() if ap_rows is None else ap_rows[col])
-        if (image_report is not None or error_report is not None) and n_img:
+        boot_ap = bootstrap is not None and bootstrap.gt_json is not None and n_img
+        six = None if ap_rows is None else ap_rows[col]
+        if (image_report is not None or error_report is not None or boot_ap) and n_img:
             if gt_json is None:                             # no device matching asked for: the reports are formed from the predictions as written
                 if predictions is None:
                     raise RuntimeError("infer: a report without the device matching (gt_json) is formed from the predictions file: write_json=False")
-                src = image_report if image_report is not None else error_report
-                areas = () if image_report is not None else (("all",),)         # the breakdown alone reads the boxes: one area range carries them
-                matching, counts = match_predictions(predictions, src.gt_json, image_ids, src.device, *areas), None
+                src = image_report if image_report is not None else error_report if error_report is not None else bootstrap
+                areas = () if image_report is not None or boot_ap else (("all",),)      # the breakdown alone reads the boxes: one area range carries them
+                matching, counts, six = match_predictions(predictions, src.gt_json, image_ids, src.device, *areas), None, None
+                matching.image_ids = image_ids
             if image_report is not None:
                 metrics.update(image_report.from_matching(matching, counts, image_ids, gt_counts, pred_counts, threshold))
                 if render is not None and output_path is not None:
                     render.from_matching(matching, counts, image_report, output_dir, threshold)
             if error_report is not None:
                 metrics.update(error_report.from_matching(matching, counts, image_ids, threshold))
+        if bootstrap is not None and n_img:
+            metrics.update(bootstrap.run(image_ids, gt_counts, pred_counts, threshold, matching if boot_ap else None, counts, six, sweep,
+                                         table.table if table is not None else None))
     return metrics, predictions
 
 
@@ -541,9 +622,11 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
     report = build_image_report(args, device)
     render = build_render(args)
     errors = build_error_report(args, device)
+    boot = build_bootstrap(args, device)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
-                       sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None), error_report=errors)
+                       sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None), error_report=errors,
+                       bootstrap=boot)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
@@ -552,6 +635,9 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
         if errors is not None and errors.report:                                                                      # and the breakdown's follow those
             from counting_detr_amd.error_report import metrics as error_metrics
             ar.update({k: metrics.pop(k) for k in error_metrics(errors.report)})
+        if boot is not None and boot.report:                                                                          # and the intervals come last
+            from counting_detr_amd.bootstrap import metrics as bootstrap_metrics
+            ar.update({k: metrics.pop(k) for k in bootstrap_metrics(boot.report)})
         metrics.update(ap_from_json(os.path.join(args.output_dir, "predictions_" + args.split + ".json"), gt_json, device=ap_device))
         metrics.update(ar)
     return metrics
@@ -582,6 +668,20 @@ def build_error_report(args, device=None):
     return ErrorReport(gt_json, torch.device(device) if on_device else None)
 
 
+def build_bootstrap(args, device=None):
+    """--bootstrap R / --bootstrap_seed S -> a Bootstrap for one pass, or None without the flag.  The AP intervals appear where
+    instances_<split>.json is there; without it only the counting intervals do, which is not an error.  `device`: where the replicates run
+    (a CUDA device unless --ap_on_host: the numpy rule, slow for AP)."""
+    if not hasattr(args, "bootstrap"):
+        from counting_detr_amd.args import check_bootstrap_flags
+        check_bootstrap_flags(args)
+        return None
+    gt_json = os.path.join(args.data_path, "instances_" + args.split + ".json")
+    on_device = device is not None and torch.device(device).type == "cuda" and not getattr(args, "ap_on_host", False)
+    return Bootstrap(args.bootstrap, getattr(args, "bootstrap_seed", 0), gt_json if os.path.isfile(gt_json) else None,
+                     torch.device(device) if on_device else None)
+
+
 def build_render(args):
     """--render_worst K / --render_ids -> a Render for one pass, or None without either flag.  Both draw what --image_report lists: without
     it this is an error (the parser says so first; a namespace built by hand meets it here)."""
@@ -597,6 +697,7 @@ def main(args):
     build_render(args)
     build_image_report(args)                                            # --image_report without instances_<split>.json: an error before anything is built
     build_error_report(args)                                            # --error_report likewise
+    build_bootstrap(args)                                               # --bootstrap_seed without --bootstrap, R out of range: likewise
     model, criterion, _ = counting_detr_amd.build_model(args)
     model.to(device)
     if args.resume:

@@ -18,6 +18,8 @@ written from then on carries "count_threshold": {"metric", "threshold", "value",
 --render_worst K / --render_ids (with --image_report) reach them too: render_<split>/ with the box overlays of the report's worst images, beside that file.
 --error_report reaches them too: WHY detections fail (duplicate / localisation / background / missed, counting_detr_amd/error_report.py) -- err_* and dAP50_*
 in the metrics (test_err_* / test_dAP50_* in the epoch log), error_report_<split>.json wherever the predictions file is written.
+--bootstrap R [--bootstrap_seed S] reaches them too: HOW FAR the numbers move when the split is resampled (counting_detr_amd/bootstrap.py) -- <K>_lo / <K>_hi in
+the metrics (test_<K>_lo / _hi in the epoch log), bootstrap_<split>.json wherever the predictions file is written; --keep_best and --calibrate_threshold decide as before.
 --nms_iou T reaches them too: greedy suppression of duplicate detections ahead of everything that counts them (counting_detr_amd/nms.py), nms_removed in the metrics.
 
   python main.py --synthetic --no_aux_loss --num_query_pattern 1 --epochs 1 -o /tmp/out
@@ -207,7 +209,7 @@ def main(args):
                                       device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
                                       per_image=per_image, sweep=_infer.build_sweep(args), image_report=_infer.build_image_report(args, device),
                                       render=_infer.build_render(args), nms_iou=getattr(args, "nms_iou", None),
-                                      error_report=_infer.build_error_report(args, device))
+                                      error_report=_infer.build_error_report(args, device), bootstrap=_infer.build_bootstrap(args, device))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
