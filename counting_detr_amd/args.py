@@ -158,6 +158,21 @@ def get_args_parser():
                         "per replicate and area range on a split of 1286 images)")
     p.add_argument("--bootstrap_seed", default=argparse.SUPPRESS, type=_seed, metavar="S",
                    help="with --bootstrap: the seed of the replicates' draws (default 0); the same seed draws the same images on every route")
+    # the four below: no attribute when they are not given; the last three need --tiles (checked when the command line is parsed)
+    p.add_argument("--tiles", default=argparse.SUPPRESS, type=_tiles, metavar="RxC",
+                   help="infer.py / main.py --eval: count past the query cap -- every image is cut into R x C overlapping tiles, the tiles are "
+                        "forwarded as one batch conditioned on the exemplars of the whole image, and each detection is kept by the tile whose "
+                        "core holds its centre (counting_detr_amd/tiling.py states the rule).  Everything after the forward reads one image of "
+                        "R * C * Q queries, at most 4096; 1x1 is the identity.  The losses are not computed (no loss_* keys in the metrics); "
+                        "needs --eval_batch_size 1, not with --eval_every.  --nms_iou removes the duplicates of objects on a seam.  With "
+                        "--device_detections: cdetr_tile_images + cdetr_tile_stitch per image.  The effect on accuracy is unmeasured")
+    p.add_argument("--tile_margin", default=argparse.SUPPRESS, type=_margin, metavar="M",
+                   help="with --tiles: pixels of the resized image a tile reaches beyond its core on every inner side (default 32)")
+    p.add_argument("--tile_scale", default=argparse.SUPPRESS, type=int, choices=[1, 2], metavar="S",
+                   help="with --tiles: 2 upsamples every tile bilinearly by 2 before the forward (default 1)")
+    p.add_argument("--tile_below", default=argparse.SUPPRESS, type=float, metavar="P",
+                   help="with --tiles: tile only the images whose exemplars are small -- mean sqrt(w * h) of the exemplars in resized pixels "
+                        "< P; every other image runs whole")
     return p
 
 
@@ -168,6 +183,7 @@ class _CheckedParser(argparse.ArgumentParser):
         ns, rest = super().parse_known_args(args, namespace)
         check_render_flags(ns, self.error)
         check_bootstrap_flags(ns, self.error)
+        check_tile_flags(ns, self.error)
         return ns, rest
 
 
@@ -193,6 +209,53 @@ def check_bootstrap_flags(ns, fail=None):
         if fail is None:
             raise ValueError(msg)
         fail(msg)
+
+
+def check_tile_flags(ns, fail=None):
+    """--tiles and what goes with it: the three companion flags need it; R * C * Q <= 4096; one image per forward; not inside training."""
+    def stop(msg):
+        if fail is None:
+            raise ValueError(msg)
+        fail(msg)
+    given = [f for f in ("tile_margin", "tile_scale", "tile_below") if hasattr(ns, f)]
+    if not hasattr(ns, "tiles"):
+        if given:
+            stop(" / ".join("--" + f for f in given) + " needs --tiles RxC: it describes how the tiles are cut")
+        return
+    from .tiling import check_capacity
+    R, C = ns.tiles
+    try:
+        check_capacity(R, C, int(getattr(ns, "num_query_position", 300)) * int(getattr(ns, "num_query_pattern", 3)))
+    except ValueError as e:
+        stop(str(e))
+    if getattr(ns, "tile_scale", 1) not in (1, 2):
+        stop(f"--tile_scale must be 1 or 2, got {ns.tile_scale}")
+    if getattr(ns, "tile_margin", 32) < 0:
+        stop(f"--tile_margin must not be negative, got {ns.tile_margin}")
+    if int(getattr(ns, "eval_batch_size", 1)) > 1:
+        stop(f"--tiles forwards the tiles of ONE image as a batch: not with --eval_batch_size {ns.eval_batch_size}")
+    if int(getattr(ns, "eval_every", 0)) > 0:
+        stop("--tiles with --eval_every: validation inside training is not built for tiles; evaluate the checkpoint with infer.py or main.py --eval")
+
+
+def _tiles(text):
+    """--tiles: `RxC` -> (R, C), both at least 1 (argparse turns the error into a usage error)."""
+    from .tiling import parse_tiles
+    try:
+        return parse_tiles(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _margin(text):
+    """--tile_margin: an integer >= 0."""
+    try:
+        M = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected an integer, got {text!r}") from None
+    if M < 0:
+        raise argparse.ArgumentTypeError(f"expected a margin of at least 0 pixels, got {M}")
+    return M
 
 
 def _replicates(text):

@@ -623,8 +623,8 @@ class Prefetcher:
     A batch that holds `raw` (collate_raw / collate_stage1_raw) gets its `image` and `mask` from ops.image_prep, launched on the same
     side stream right after the copies; `images` / `device_resampled` count what has gone through it."""
 
-    def __init__(self, loader, device):
-        self.loader, self.device = loader, torch.device(device)
+    def __init__(self, loader, device, host_keys=()):
+        self.loader, self.device, self.host_keys = loader, torch.device(device), tuple(host_keys)      # host_keys: also kept as `<key>_host`
         self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         self.images = self.device_resampled = 0
 
@@ -636,6 +636,7 @@ class Prefetcher:
                 t = t.pin_memory() if not t.is_pinned() else t
             return t.to(self.device, non_blocking=True)
         out = {k: mv(v) for k, v in batch.items() if k not in ("targets", "raw")}
+        out.update({k + "_host": batch[k] for k in self.host_keys if k in batch})
         if "targets" in batch:
             out["targets"] = [{k: mv(v) for k, v in t.items()} for t in batch["targets"]]
         if "raw" in batch:                      # the un-resized pixels went across: resize + normalise + pad there, in this stream
@@ -666,7 +667,7 @@ class Prefetcher:
             if self.stream is not None:
                 torch.cuda.current_stream(self.device).wait_stream(self.stream)
                 for v in list(nxt.values()) + [x for t in nxt.get("targets", ()) for x in t.values()]:
-                    if torch.is_tensor(v):
+                    if torch.is_tensor(v) and v.is_cuda:
                         v.record_stream(torch.cuda.current_stream(self.device))
             cur, nxt = nxt, stage()
             yield cur

@@ -1847,10 +1847,11 @@ class InferenceEngine:
                 m.refresh("fwd")
 
     @torch.no_grad()
-    def _run(self, images, mask, rects):
+    def _run(self, images, mask, rects, group=1):
         from . import ops
         with ops.scope(MIRROR=self.mirror):
-            outputs, ref = self.model(NestedTensor(images, mask), rects=rects)
+            outputs, ref = self.model(NestedTensor(images, mask), rects=rects) if group == 1 else \
+                self.model(NestedTensor(images, mask), rects=rects, group=group)
         counts, keep, prob = count_from_logits(outputs["pred_logits"], self.threshold)
         return counts, keep, outputs, ref, prob
 
@@ -1870,19 +1871,27 @@ class InferenceEngine:
 
     @_scoped
     @torch.no_grad()
-    def __call__(self, samples, rects, next_samples=None):
+    def __call__(self, samples, rects, next_samples=None, group=1):
+        """`group` > 1 (tiled inference): the batch is groups of `group` consecutive tiles of one image each, conditioned on the exemplars pooled
+        over the group (AnchorDETR.forward); such a call has a captured forward of its own and ignores the `next_samples` look-ahead."""
         from . import _ffi, ops
         nt = samples if hasattr(samples, "decompose") else nested_tensor_from_tensor_list(samples)
         images, mask = nt.decompose()
         self.stats["calls"] += 1
+        group = int(group)
+        if group != 1:
+            if group < 1 or images.shape[0] % group:
+                raise ValueError(f"InferenceEngine: a batch of {images.shape[0]} tiles does not divide into groups of {group}")
+            self.stats["grouped_calls"] = self.stats.get("grouped_calls", 0) + 1
+            next_samples = None
         if self.trainer is not None:
             self._check_disarmed()
             _ = self.mirror                        # a rebuilt trainer mirror drops the graphs BEFORE the lookup below
         if not self.graphs or not images.is_cuda:
-            return self._run(images, mask, rects)
+            return self._run(images, mask, rects, group)
         body = self.model.backbone.body if self._prefetch_on else None
         fs = self._frozen_for(images.shape) if body is not None else None
-        key = (tuple(images.shape), tuple(rects.shape))
+        key = (tuple(images.shape), tuple(rects.shape), group)
         e = self._cache.pop(key, None)
         if e is None:
             while len(self._cache) >= max(self.max_graphs, 1):
@@ -1901,7 +1910,7 @@ class InferenceEngine:
                     after = lambda: _ffi.check(_ffi.lib().cdetr_flag_signal(sig.data_ptr(), _ffi.stream_ptr()), "cdetr_flag_signal")      # noqa: E731
                 # a LINEAR graph (no in-graph forks): hipGraphLaunch enqueues it in ~0.1 ms of host time (2.7 ms with forks)
                 with ops.scope(BRANCH_BESIDE=0, AFTER_BACKBONE=after), _no_gc():
-                    self._run(*st)                     # lazily cached tables of this shape exist before the capture
+                    self._run(*st, group)                     # lazily cached tables of this shape exist before the capture
                     if after is not None:              # (that run signalled too: keep `consumed` level with the counter)
                         with torch.cuda.stream(self._pf_stream):
                             _ffi.check(_ffi.lib().cdetr_flag_wait(self._sig.data_ptr(), self._sig.data_ptr() + 4, 0, 0, _ffi.stream_ptr()), "cdetr_flag_wait")
@@ -1911,7 +1920,7 @@ class InferenceEngine:
                     if self._pool is None:
                         self._pool = torch.cuda.graph_pool_handle()
                     with torch.cuda.graph(g, pool=self._pool, stream=self._stream):
-                        out = self._run(*st)
+                        out = self._run(*st, group)
             finally:
                 if fs is not None:
                     body.frozen_input = None

@@ -5,7 +5,7 @@ images it fails, `--render_worst` shows them; this says what went wrong, because
   duplicate     the same object counted twice                       -> --nms_iou, fewer query patterns
   localisation  a box on an object, IoU < 0.5 with it               -> box loss weights, stage-1 pseudo-box quality
   background    a box on nothing                                    -> the threshold
-  missed        no box anywhere near an object                      -> the threshold, the query count
+  missed        no box anywhere near an object                      -> the threshold, the query count (--tiles)
 
 The reference has nothing like it.  This module is the RULE and the checker: csrc/error_report.hip (cdetr_coco_errors, one launch for a
 split) equals `classify` bit for bit (tests/test_error_report_cpu.py pins `classify` to a loop-by-loop restatement, _gpu.py the kernel to it).

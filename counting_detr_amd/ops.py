@@ -864,9 +864,27 @@ def mask_prep(mask, h, w):
     return mi
 
 
-def exemplar_fwd_raw(x, rects, extent, per_image):
+def forward_only_group(group):
+    """The `group` argument as the model hands it to ExemplarFeatureFn / AggrProjFn (an autograd.Function's forward cannot see the caller's grad
+    mode, so the model asks here, once for both paths): a group > 1 with gradients enabled is an error."""
+    group = int(group)
+    if group != 1 and torch.is_grad_enabled():
+        raise RuntimeError(f"exemplar feature: group = {group} is forward only (tiled inference); it was called with gradients enabled")
+    return group
+
+
+def exemplar_fwd_raw(x, rects, extent, per_image, group=1):
+    """-> (pf, idx, inv_cnt).  `group` > 1 (tiled inference: the batch is groups of `group` consecutive tiles of one image each, B % group == 0):
+    every tile of a group gets the feature pooled over the whole group (cdetr_exemplar_group_fwd; inv_cnt is None: forward only, see
+    `forward_only_group`)."""
     B, h, w, Cc = x.shape
     K = rects.shape[1]
+    group = int(group)
+    if group != 1:
+        if not per_image:
+            raise RuntimeError(f"exemplar feature: group = {group} needs exemplar_mode per_image (every tile has its own rects and extent)")
+        pf, idx = exemplar_group_fwd(x, rects, extent, group)
+        return pf, idx, None
     idx = torch.empty((B, K), device=x.device, dtype=torch.int32)
     inv_cnt = torch.empty(B, device=x.device, dtype=torch.float32)
     pf = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
@@ -875,16 +893,35 @@ def exemplar_fwd_raw(x, rects, extent, per_image):
     return pf, idx, inv_cnt
 
 
+def exemplar_group_fwd(x, rects, extent, group, events=None):
+    """cdetr_exemplar_group_fwd: x fp32 NHWC [B, h, w, C], rects fp32 [B, K, 4] (x2 < 0: absent), extent fp32 [B, 2], groups of `group`
+    consecutive tiles (B % group == 0) -> (pf fp32 [B, C]: the feature pooled over a group, the same row for each of its tiles; idx int32
+    [B, K]).  counting_detr_amd/tiling.py states the rule (`group_feature` is the host form); group = 1 equals cdetr_exemplar_fwd bit for bit."""
+    _expect("exemplar_group_fwd", torch.float32, x=x, rects=rects, extent=extent)
+    B, group = x.shape[0], int(group)
+    if x.dim() != 4 or rects.dim() != 3 or tuple(rects.shape) != (B, rects.shape[1], 4) or tuple(extent.shape) != (B, 2) or group < 1 or B % group:
+        raise RuntimeError(f"exemplar_group_fwd: x [B, h, w, C], rects [B, K, 4], extent [B, 2], B % group == 0 expected, got {tuple(x.shape)}, "
+                           f"{tuple(rects.shape)}, {tuple(extent.shape)}, group = {group}")
+    _, h, w, Cc = x.shape
+    K = rects.shape[1]
+    idx = torch.empty((B, K), device=x.device, dtype=torch.int32)
+    pf = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
+    with _between(events):
+        check(lib().cdetr_exemplar_group_fwd(ptr(x), ptr(rects), ptr(extent), B, group, h, w, Cc, K, ptr(idx), ptr(pf), stream_ptr()),
+              "cdetr_exemplar_group_fwd")
+    return pf, idx
+
+
 class ExemplarFeatureFn(torch.autograd.Function):
     """pf[b] = mean_k x[b, cell(b, k)]: the exemplar feature of A2/models/backbone.py:116-131 (`per_image`: image b is conditioned on
     rects[b] scaled by its un-padded extent; else the reference's rects[0]-for-the-whole-batch rule).  x NHWC [B,h,w,C] -> [B,C]."""
 
     @staticmethod
-    def forward(ctx, x, rects, extent, per_image):
+    def forward(ctx, x, rects, extent, per_image, *group):          # (*group: at most one more argument, the group size of exemplar_fwd_raw)
         x = x.contiguous()
-        pf, idx, inv_cnt = exemplar_fwd_raw(x, rects.contiguous().to(torch.float32), extent, per_image)
+        pf, idx, inv_cnt = exemplar_fwd_raw(x, rects.contiguous().to(torch.float32), extent, per_image, *group)
         ctx.save_for_backward(idx, inv_cnt)
-        ctx.shape = x.shape
+        ctx.shape, ctx.extra = x.shape, len(group)
         return pf
 
     @staticmethod
@@ -894,7 +931,7 @@ class ExemplarFeatureFn(torch.autograd.Function):
         dx = torch.zeros(ctx.shape, device=dpf.device, dtype=torch.float32)
         check(lib().cdetr_exemplar_bwd(ptr(dpf.contiguous()), ptr(idx), ptr(inv_cnt), ptr(dx), B, h * w, Cc, idx.shape[1], stream_ptr()),
               "cdetr_exemplar_bwd")
-        return dx, None, None, None
+        return (dx, None, None, None) + (None,) * ctx.extra
 
 
 class AggrProjFn(torch.autograd.Function):
@@ -907,13 +944,13 @@ class AggrProjFn(torch.autograd.Function):
     dx[b, cell] += dpf[b] / K."""
 
     @staticmethod
-    def forward(ctx, x, rects, extent, per_image, wparam, bparam):
+    def forward(ctx, x, rects, extent, per_image, wparam, bparam, *group):          # (*group: as ExemplarFeatureFn's)
         B, h, w, Cc = x.shape
         W2d = wparam.detach().reshape(wparam.shape[0], -1)                 # [d, 2C]
         assert W2d.is_contiguous() and W2d.shape[1] == 2 * Cc
         d = W2d.shape[0]
         x = x.contiguous()
-        pf, idx, inv_cnt = exemplar_fwd_raw(x, rects.contiguous().to(torch.float32), extent, per_image)
+        pf, idx, inv_cnt = exemplar_fwd_raw(x, rects.contiguous().to(torch.float32), extent, per_image, *group)
         Weff = torch.empty((B, d, Cc), device=x.device, dtype=torch.float32)
         WeffT = torch.empty((B, Cc, d), device=x.device, dtype=torch.float32)
         check(lib().cdetr_aggr_weight_fwd(ptr(W2d), ptr(pf), ptr(Weff), ptr(WeffT), B, d, Cc, stream_ptr()), "cdetr_aggr_weight_fwd")
@@ -921,7 +958,7 @@ class AggrProjFn(torch.autograd.Function):
         # the bias pointer is shared by the batch items
         gemm_raw(x, Cc, Weff, Cc, y, d, h * w, d, Cc, bias=bparam.detach(), batch=B, sA=h * w * Cc, sB=d * Cc, sC=h * w * d)
         ctx.save_for_backward(x, pf, WeffT, idx, inv_cnt)
-        ctx.wparam, ctx.bparam, ctx.d = wparam, bparam, d
+        ctx.wparam, ctx.bparam, ctx.d, ctx.extra = wparam, bparam, d, len(group)
         return y
 
     @staticmethod
@@ -942,7 +979,7 @@ class AggrProjFn(torch.autograd.Function):
         gw = grad_buffer(wparam).reshape(d, -1) if wparam.requires_grad else None
         check(lib().cdetr_aggr_weight_bwd(ptr(dWeff), ptr(pf), ptr(W2d), ptr(gw), ptr(dpf), B, d, Cc, stream_ptr()), "cdetr_aggr_weight_bwd")
         check(lib().cdetr_exemplar_bwd(ptr(dpf), ptr(idx), ptr(inv_cnt), ptr(dx), B, h * w, Cc, idx.shape[1], stream_ptr()), "cdetr_exemplar_bwd")
-        return dx, None, None, None, None, None
+        return (dx, None, None, None, None, None) + (None,) * ctx.extra
 
 
 class TileParamFn(torch.autograd.Function):
@@ -2539,6 +2576,59 @@ def nms_suppress(prob, boxes, orig_hw, threshold, iou, out=None, removed=None, e
     with _between(events):
         check(lib().cdetr_nms_suppress(C.byref(d), stream_ptr()), "cdetr_nms_suppress")
     return out, removed
+
+
+def tile_images(image, records, Hm, Wm, tiles=None, mask=None, events=None):
+    """cdetr_tile_images: image fp32 [3, H, W] and records int32 [T, 5] = (x0, y0, width, height, scale) per tile, both on the device ->
+    (tiles fp32 [T, 3, Hm, Wm], mask bool [T, Hm, Wm], True = padding), equal to tiling.tile_images (the host form) bit for bit.  One launch on
+    the current stream; it writes every element of both outputs, a record that does not fit gives an all-padding tile.  `tiles` / `mask`:
+    tensors to write into.  events: a pair of torch.cuda.Event recorded right before / after the launch (tools/tiling_time.py)."""
+    _expect("tile_images", torch.float32, image=image, tiles=tiles)
+    _expect("tile_images", torch.int32, records=records)
+    _expect("tile_images", torch.bool, mask=mask)
+    Hm, Wm = int(Hm), int(Wm)
+    if image.dim() != 3 or image.shape[0] != 3 or records.dim() != 2 or records.shape[1] != _ffi.DEFINES["TILE_RECORD_INTS"] or records.shape[0] < 1 \
+            or records.device != image.device:
+        raise RuntimeError(f"tile_images: image [3, H, W] and records [T, 5] on one device expected, got {tuple(image.shape)} on {image.device}, "
+                           f"{tuple(records.shape)} on {records.device}")
+    T = records.shape[0]
+    for name, t, shape in (("tiles", tiles, (T, 3, Hm, Wm)), ("mask", mask, (T, Hm, Wm))):
+        if t is not None and (tuple(t.shape) != shape or t.device != image.device):
+            raise RuntimeError(f"tile_images: `{name}` must be {shape} on {image.device}, got {tuple(t.shape)} on {t.device}")
+    tiles = torch.empty((T, 3, Hm, Wm), dtype=torch.float32, device=image.device) if tiles is None else tiles
+    mask = torch.empty((T, Hm, Wm), dtype=torch.bool, device=image.device) if mask is None else mask
+    with _between(events):
+        check(lib().cdetr_tile_images(ptr(image), image.shape[1], image.shape[2], ptr(records), T, Hm, Wm, ptr(tiles), ptr(mask), stream_ptr()),
+              "cdetr_tile_images")
+    return tiles, mask
+
+
+def tile_stitch(prob, boxes, points, coef, slots, H, W, out=None, events=None):
+    """cdetr_tile_stitch: prob fp32 [T, Q], boxes fp32 [T, Q, 4] cxcywh, points fp32 [T, Q, 2] of an image's T tiles and coef fp32 [T, 8]
+    (tiling.Plan.coef) -> (prob [1, Qv], boxes [1, Qv, 4], points [1, Qv, 2]) of the virtual image, Qv = slots * Q, in whole-image coordinates;
+    a query not centred in its tile's core, and every query of the slots T .. slots - 1, has prob NaN.  Equal to tiling.stitch (the host form)
+    bit for bit.  `out`: the three tensors to write into.  One launch on the current stream, nothing comes back to the host; slots * Q >
+    4096 raises before any launch.  events: a pair of torch.cuda.Event recorded right before / after the launch."""
+    _expect("tile_stitch", torch.float32, prob=prob, boxes=boxes, points=points, coef=coef)
+    if prob.dim() != 2 or tuple(boxes.shape) != tuple(prob.shape) + (4,) or tuple(points.shape) != tuple(prob.shape) + (2,) \
+            or tuple(coef.shape) != (prob.shape[0], _ffi.DEFINES["TILE_COEF_FLOATS"]):
+        raise RuntimeError(f"tile_stitch: prob [T, Q], boxes [T, Q, 4], points [T, Q, 2], coef [T, 8] expected, got {tuple(prob.shape)}, "
+                           f"{tuple(boxes.shape)}, {tuple(points.shape)}, {tuple(coef.shape)}")
+    for name, t in (("boxes", boxes), ("points", points), ("coef", coef)):
+        if t.device != prob.device:
+            raise RuntimeError(f"tile_stitch: `{name}` on {t.device}, prob on {prob.device}")
+    (T, Q), slots = prob.shape, int(slots)
+    Qv = max(slots, 0) * Q
+    if out is None:
+        out = (torch.empty((1, Qv), dtype=torch.float32, device=prob.device), torch.empty((1, Qv, 4), dtype=torch.float32, device=prob.device),
+               torch.empty((1, Qv, 2), dtype=torch.float32, device=prob.device))
+    _expect("tile_stitch", torch.float32, prob_out=out[0], boxes_out=out[1], points_out=out[2])
+    if [tuple(o.shape) for o in out] != [(1, Qv), (1, Qv, 4), (1, Qv, 2)] or any(o.device != prob.device for o in out):
+        raise RuntimeError(f"tile_stitch: `out` must be [1, {Qv}], [1, {Qv}, 4], [1, {Qv}, 2] on {prob.device}, got {[tuple(o.shape) for o in out]}")
+    with _between(events):
+        check(lib().cdetr_tile_stitch(ptr(prob), ptr(boxes), ptr(points), ptr(coef), T, Q, slots, int(H), int(W), ptr(out[0]), ptr(out[1]),
+                                      ptr(out[2]), stream_ptr()), "cdetr_tile_stitch")
+    return out
 
 
 class CriterionFn(torch.autograd.Function):

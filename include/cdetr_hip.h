@@ -868,6 +868,36 @@ typedef struct {
 } cdetr_emit_pseudo_labels_desc;
 int cdetr_emit_pseudo_labels(const cdetr_emit_pseudo_labels_desc* d, void* stream);
 
+/* ---- tiled inference past the query cap (csrc/tiling.hip; infer.py --tiles RxC): the device steps around the grouped forward of an image's
+ * tiles, EQUAL to the host rule of counting_detr_amd/tiling.py; FMA contraction is switched off in this translation unit.
+ * cdetr_tile_images: ONE launch per image.  image [3][H][W] fp32 and one record of CDETR_TILE_RECORD_INTS int32 per tile = { x0, y0, width,
+ *   height (the crop, in pixels of the image), scale (1 or 2) } -> tiles [T][3][Hm][Wm] fp32 and mask [T][Hm][Wm] bytes (1 = padding); every
+ *   element of both is written.  Scale 1 copies the crop.  Scale 2: output sample j of an axis takes the source pixel x0 + j / 2 with weight
+ *   0.75 and its left (j even) or right (j odd) neighbour, clamped to the IMAGE, with 0.25; horizontal pass first, the vertical pass over its
+ *   result, each pass 0.75f * a + 0.25f * b rounded per operation.  A record is range-checked on the device before it addresses anything
+ *   (inside the image, width * scale <= Wm, height * scale <= Hm): a bad one gives an all-padding tile.  Limits: sides <= CDETR_TILE_MAX_SIDE,
+ *   T <= CDETR_TILE_MAX_VIRTUAL, CDETR_ERR_UNSUPPORTED beyond.
+ * cdetr_exemplar_group_fwd: cdetr_exemplar_fwd with per_image set for tiles that share their exemplars: x [B][h*w][C], rects [B][K][4],
+ *   extent [B][2], groups of G consecutive tiles (B % G == 0).  pf [B][C]: every tile of a group gets (sum of x[tile][cell] over the group's
+ *   tiles in order and k in order, present rows only, fp32 running sum) * (1 / max(cnt, 1)); idx [B][K]: cell or -1.  Forward only.  G = 1
+ *   equals cdetr_exemplar_fwd bit for bit.
+ * cdetr_tile_stitch: prob [T][Q], boxes [T][Q][4] cxcywh, points [T][Q][2] of an image's tiles and CDETR_TILE_COEF_FLOATS fp32 per tile =
+ *   { ax, ox, ay, oy, lo_x, hi_x, lo_y, hi_y } -> the virtual image of Qv = slots * Q queries (virtual query t * Q + q = query q of tile t):
+ *   centres and points v * a + o, sizes v * a (one fp32 multiply, one fp32 add); prob kept iff lo <= centre * (float)W / (float)H < hi on
+ *   both axes, an infinite bound being no bound, NaN otherwise; slots T .. slots - 1 are NaN with zero boxes and points.  Every one of the
+ *   Qv entries of the three outputs is written once, no atomics; outputs must not alias inputs.  Limit: slots * Q <= CDETR_TILE_MAX_VIRTUAL
+ *   (what cdetr_emit_detections and cdetr_nms_suppress take), CDETR_ERR_UNSUPPORTED beyond.                                            */
+#define CDETR_TILE_RECORD_INTS 5
+#define CDETR_TILE_COEF_FLOATS 8
+#define CDETR_TILE_MAX_SIDE 16384
+#define CDETR_TILE_MAX_VIRTUAL 4096
+int cdetr_tile_images(const float* image, int32_t H, int32_t W, const int32_t* records, int32_t T, int32_t Hm, int32_t Wm, float* tiles,
+                      uint8_t* mask, void* stream);
+int cdetr_exemplar_group_fwd(const float* x, const float* rects, const float* extent, int32_t B, int32_t G, int32_t h, int32_t w, int32_t C,
+                             int32_t K, int32_t* idx, float* pf, void* stream);
+int cdetr_tile_stitch(const float* prob, const float* boxes, const float* points, const float* coef, int32_t T, int32_t Q, int32_t slots,
+                      int32_t H, int32_t W, float* prob_out, float* boxes_out, float* points_out, void* stream);
+
 const char* cdetr_last_error(void);
 int cdetr_abi_version(void);
 /* Stream plumbing of the trainer (no reference counterpart: the reference runs one stream and drains it every step, A2/engine.py:33-57).

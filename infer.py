@@ -72,8 +72,23 @@ predictions file ({"split", "threshold", "replicates", "seed", "level", "metrics
 where it lies (cdetr_bootstrap_counts); any other run on a GPU matches the written predictions there for the same kernels; `--ap_on_host` is the numpy rule,
 slow for AP.  Same bytes on every route.  Without the flag nothing changes.
 
+`--tiles RxC` (`--tile_margin M`, default 32; `--tile_scale S`, 1 or 2, default 1; `--tile_below P`; off without --tiles, and nothing changes) counts PAST
+the query cap: the model has Q queries, so no image can count more than Q objects.  Every image is cut into R x C overlapping tiles (cores on a
+32-pixel grid that partition the image, each tile reaching M pixels beyond its core, optionally upsampled by 2), the tiles run as ONE grouped forward
+in which every tile is conditioned on the exemplar feature pooled over all tiles of the image (cdetr_exemplar_group_fwd), and the stitch puts their
+outputs back into whole-image coordinates as one virtual image of R * C * Q queries (at most 4096) in which a query keeps its prob only in the tile
+whose core holds its centre -- everywhere else it is NaN (counting_detr_amd/tiling.py states the rule).  It is one more filter between the forward and
+the first reader: the store, the sweep, the one matching, the reports, the intervals, the overlays and the predictions file work on [1, R * C * Q, .]
+tensors unchanged, and --nms_iou, which runs after the stitch, removes the second detection of an object that straddles a seam.  --tile_below P
+tiles only the images whose exemplars are small (mean sqrt(w h) in resized pixels < P, known on the host); the others run whole.  The losses are
+not computed under --tiles (no loss_* / class_error / cardinality_error in the metrics); --eval_batch_size must be 1; 1x1 is the identity.  The host
+loop cuts and stitches with tiling.py's numpy (the checker); with --device_detections one cdetr_tile_images and one cdetr_tile_stitch launch per image
+do the same bit for bit, nothing awaited.  Whether tiling lowers MAE on trained FSC-147 weights is UNMEASURED.
+
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --tiles 2x2 --nms_iou 0.5
+  python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --tiles 2x2 --tile_scale 2 --tile_below 24
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --error_report
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --bootstrap 1000
   python infer.py -dp /data/FSC147 --split val --resume out/detr_retrain.pth -o out --device_detections --image_report
@@ -224,7 +239,7 @@ class Render:
 @torch.no_grad()
 def infer(model, criterion, data_loader, device, output_dir, split="test", threshold=0.5, graphs=True, device_detections=False, gt_json=None,
           per_image=False, engine=None, write_json=True, sweep=None, image_report=None, render=None, nms_iou=None, error_report=None,
-          bootstrap=None):
+          bootstrap=None, tiles=None):
     """-> (metrics dict, predictions dict); writes predictions_<split>.json like A2/infer.py:28-121.  The forward + counting rule
     runs through engine.InferenceEngine (pre-split weight images, one captured HIP graph per image shape; `graphs=False`: eager).
     `device_detections`: the post-forward work on the device (`_infer_device`): the same file, bytes and all, the same metrics; with `gt_json`
@@ -254,7 +269,13 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
     one of the predictions as written -- and does not need an image report.
     `bootstrap` (a Bootstrap; None: off, and nothing changes): the metrics gain <K>_lo / <K>_hi for MAE / RMSE / NAE / SRE and, where
     `bootstrap.gt_json` is set, for the six AP numbers, and bootstrap_<split>.json is written wherever the predictions file is.  The AP
-    replicates read the SAME one matching as the reports (with `device_detections` and `gt_json` the store's, its flags where they lie)."""
+    replicates read the SAME one matching as the reports (with `device_detections` and `gt_json` the store's, its flags where they lie).
+    `tiles` (--tiles; a tiling.Tiling, None: off, and nothing changes): every image is cut into overlapping tiles, the tiles run as ONE grouped
+    forward conditioned on the image's pooled exemplars, and the stitch turns their outputs into `prob`, `pred_boxes` and `ref_points` of shape
+    [1, R * C * Q, .] in whole-image coordinates, a query outside its tile's core NaN (counting_detr_amd/tiling.py states the rule) -- one more
+    filter between the forward and the first reader, ahead of `nms_iou`.  The host loop cuts and stitches with tiling.py's numpy, the device loop
+    with cdetr_tile_images / cdetr_tile_stitch.  The criterion is not called: a stitched set of queries is not a training output, the metrics
+    carry no loss_* / class_error / cardinality_error.  One image per batch."""
     from counting_detr_amd import threshold_sweep as ts
     threshold = ts.widen(threshold)
     if nms_iou is not None:
@@ -286,7 +307,7 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         engine.sync()                   # the epoch's last optimizer step came after the last refresh of the trainer's forward images
     if device_detections:
         out = _infer_device(engine, criterion, data_loader, torch.device(device), output_path, threshold, gt_json, per_image, sweep, image_report,
-                            render, output_dir, nms_iou, error_report, bootstrap)
+                            render, output_dir, nms_iou, error_report, bootstrap, tiles)
         _write_sweep(sweep, output_dir, split)
         if image_report is not None and output_path is not None:
             image_report.write(output_dir)
@@ -315,7 +336,11 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
         image, mask = ret["image"], ret["mask"]
         rects = ret["ex_rects"].to(device)
         targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
-        _, keep, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects, next_samples=next_image)      # forward + :75-81
+        if tiles is None:
+            _, keep, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects, next_samples=next_image)      # forward + :75-81
+        else:                                       # the tiles of this image as one grouped forward, stitched by the numpy rule
+            outputs, ref_points, prob = _tiled_forward(engine, tiles, image, mask, ret, on_device=False)
+            keep = prob >= threshold
         if nms_iou is not None:                     # the filter: everything below reads the suppressed queries as NaN
             raw = prob.cpu().numpy()
             kept_h, _ = nms.suppress(raw, outputs["pred_boxes"].cpu().numpy(), [[int(x) for x in hw] for hw in ret["orig_size"]],
@@ -323,7 +348,9 @@ def infer(model, criterion, data_loader, device, output_dir, split="test", thres
             nms_removed += int((ts.kept(raw, threshold) & ~ts.kept(kept_h, threshold)).sum())
             prob = torch.from_numpy(kept_h).to(prob.device)
             keep = prob >= threshold
-        if per_image:
+        if tiles is not None:                       # no losses: the criterion describes whole-image training outputs
+            pass
+        elif per_image:
             for k, v in criterion.per_image(outputs, targets).items():
                 for x in v.tolist():                # float(v[b]) in image order
                     loss_sum[k] = loss_sum.get(k, 0.0) + x
@@ -422,7 +449,7 @@ def _num_images(data_loader):
 
 
 def _infer_device(engine, criterion, data_loader, device, output_path, threshold, gt_json, per_image=False, sweep=None, image_report=None,
-                  render=None, output_dir=None, nms_iou=None, error_report=None, bootstrap=None):
+                  render=None, output_dir=None, nms_iou=None, error_report=None, bootstrap=None, tiles=None):
     """The loop of `infer` with nothing coming back to the host inside it.  Per batch: forward, losses into row i of a device buffer (`per_image`:
     cdetr_criterion_eval's [B, 7] rows into B rows, one per image), one
     cdetr_emit_detections call into an ops.DetectionStore (wire records in query order + evaluation records in COCOeval's order), original sizes
@@ -437,7 +464,9 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     prefix of every image that `threshold` keeps, min(its count there, max_det).
     Without `gt_json` the report and the overlays are formed from the predictions dict as written (`match_predictions`, once for both).
     `nms_iou`: one cdetr_nms_suppress launch per batch at the store's threshold replaces `prob` before the emit and the sweep's count read it;
-    the number of suppressed queries with raw prob >= `threshold` is accumulated in a device scalar and read after the loop."""
+    the number of suppressed queries with raw prob >= `threshold` is accumulated in a device scalar and read after the loop.
+    `tiles`: one cdetr_tile_images launch cuts the image, the tiles run as one grouped forward, one cdetr_tile_stitch launch leaves prob / boxes
+    / points of R * C * Q virtual queries where the suppression and the emit read them; the store is sized for that many queries; no losses."""
     import numpy as np
     from counting_detr_amd import ops
     from counting_detr_amd import threshold_sweep as ts
@@ -451,8 +480,12 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             image, mask = ret["image"].to(device), ret["mask"].to(device)
             rects = ret["ex_rects"].to(device)
             targets = [{k: v.to(device) for k, v in t.items()} for t in ret["targets"]]
-            _, _, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects)
-            loss_dict = criterion.per_image(outputs, targets) if per_image else criterion(outputs, targets)
+            if tiles is None:
+                _, _, outputs, ref_points, prob = engine(NestedTensor(image, mask), rects)
+                loss_dict = criterion.per_image(outputs, targets) if per_image else criterion(outputs, targets)
+            else:
+                outputs, ref_points, prob = _tiled_forward(engine, tiles, image, mask, ret, on_device=True)
+                loss_dict = {}
             B, Q = prob.shape
             if store is None:
                 store = ops.DetectionStore(N, Q, device, threshold=threshold if sweep is None else sweep.thresholds[0], max_det=MAX_DETS)
@@ -463,7 +496,8 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
             if n_img + B > N or list(loss_dict) != loss_keys:
                 raise RuntimeError(f"infer: the loader yields more than its {N} images, or the criterion changed its losses")
             if not per_image:
-                loss_buf[n_batch].copy_(torch.stack([v.detach().reshape(()).to(torch.float64) for v in loss_dict.values()]))
+                if loss_keys:
+                    loss_buf[n_batch].copy_(torch.stack([v.detach().reshape(()).to(torch.float64) for v in loss_dict.values()]))
                 n_targets.append(len(targets))
                 n_batch += 1
             else:
@@ -556,6 +590,42 @@ def _infer_device(engine, criterion, data_loader, device, output_path, threshold
     return metrics, predictions
 
 
+def _tiled_forward(engine, tiles, image, mask, ret, on_device):
+    """One image under --tiles -> (outputs {"pred_boxes": [1, Qv, 4]}, ref_points [1, Qv, 2], prob [1, Qv]) on the image's device, Qv = R * C * Q:
+    the plan of this image (its size and, under --tile_below, its exemplars, known on the host), the tile batch and the tile rects, ONE grouped
+    forward, the stitch.  `on_device`: cdetr_tile_images and cdetr_tile_stitch, nothing awaited; else tiling.py's numpy rule, the checker.  An
+    image whose plan is one whole-image tile is forwarded as it is."""
+    from counting_detr_amd import tiling
+    if image.shape[0] != 1:
+        raise ValueError(f"infer: --tiles runs one image per batch, the loader gave {image.shape[0]} (--eval_batch_size must be 1)")
+    rects_h = ret.get("ex_rects_host", ret["ex_rects"])[0].cpu().numpy()          # the loader's own host tensor: no device is asked
+    plan = tiles.plan_for(image.shape[2], image.shape[3], rects_h)
+    device, T = image.device, plan.T
+    trects = torch.from_numpy(tiling.tile_rects(rects_h, plan)).to(device, non_blocking=True)
+    if on_device:                                   # the plan's two small tables go up once per image size
+        from counting_detr_amd import ops
+        tables = plan.__dict__.setdefault("_tables", {})
+        if device not in tables:
+            tables[device] = (torch.from_numpy(plan.records).to(device), torch.from_numpy(plan.coef).to(device))
+        records, coef = tables[device]
+    if plan.whole:
+        timg, tmask = image, mask
+    elif on_device:
+        timg, tmask = ops.tile_images(image[0].contiguous(), records, plan.Hm, plan.Wm)
+    else:
+        t_h, m_h = tiling.tile_images(image[0].cpu().numpy(), plan)
+        timg, tmask = torch.from_numpy(t_h).to(device), torch.from_numpy(m_h).to(device)
+    _, _, touts, tref, tprob = engine(NestedTensor(timg, tmask), trects, group=T)
+    Q = tprob.shape[1]
+    if on_device:
+        prob, boxes, points = ops.tile_stitch(tprob.contiguous(), touts["pred_boxes"].contiguous(), tref.reshape(T, Q, 2).contiguous(), coef,
+                                              plan.slots, plan.H, plan.W)
+    else:
+        p_h, b_h, r_h = tiling.stitch(tprob.cpu().numpy(), touts["pred_boxes"].cpu().numpy(), tref.reshape(T, Q, 2).cpu().numpy(), plan)
+        prob, boxes, points = (torch.from_numpy(a)[None].to(device) for a in (p_h, b_h, r_h))
+    return {"pred_boxes": boxes}, points, prob
+
+
 def counting_metrics_from_json(pred_json, gt_json, threshold=0.5):
     """MAE / RMSE / NAE / SRE from a predictions json and the split's `instances_<split>.json` (A2/eval_all.py:141-270:
     predicted count = #annotations with score >= threshold per image, ground truth = #instances)."""
@@ -584,8 +654,8 @@ def eval_loader(args, device):
         dl = DataLoader(ds, batch_sampler=data.SizeBucketBatchSampler(ds, B), collate_fn=collate_fn, num_workers=args.num_workers)
     else:
         dl = DataLoader(ds, batch_size=1, shuffle=False, collate_fn=collate_fn, num_workers=args.num_workers)
-    if raw:
-        dl = data.Prefetcher(dl, device)
+    if raw:                                                             # --tiles plans on the host: the exemplar rects also stay there
+        dl = data.Prefetcher(dl, device, host_keys=("ex_rects",)) if hasattr(args, "tiles") else data.Prefetcher(dl, device)
     return dl, B > 1
 
 
@@ -623,10 +693,11 @@ def evaluate_split(model, criterion, dl, per_image, device, args, engine=None, w
     render = build_render(args)
     errors = build_error_report(args, device)
     boot = build_bootstrap(args, device)
+    tiles = build_tiling(args)
     metrics, _ = infer(model, criterion, dl, device, args.output_dir, split=args.split, threshold=threshold, device_detections=on_device,
                        gt_json=gt_json if ap_in_loop else None, per_image=per_image, engine=engine, write_json=write_json or ap_from_file,
                        sweep=sweep, image_report=report, render=render, nms_iou=getattr(args, "nms_iou", None), error_report=errors,
-                       bootstrap=boot)
+                       bootstrap=boot, tiles=tiles)
     if ap_from_file:
         from counting_detr_amd.coco_ap import ap_from_json
         # the matching runs on the device the detections came from (one cdetr_coco_match launch); --ap_on_host: the interpreted path, same numbers
@@ -682,6 +753,18 @@ def build_bootstrap(args, device=None):
                      torch.device(device) if on_device else None)
 
 
+def build_tiling(args):
+    """--tiles RxC / --tile_margin / --tile_scale / --tile_below -> a tiling.Tiling for one pass, or None without --tiles.  The flags are
+    checked again here (the parser says so first; a namespace built by hand meets it here)."""
+    from counting_detr_amd.args import check_tile_flags
+    check_tile_flags(args)
+    if not hasattr(args, "tiles"):
+        return None
+    from counting_detr_amd.tiling import Tiling
+    R, C = args.tiles
+    return Tiling(R, C, getattr(args, "tile_margin", 32), getattr(args, "tile_scale", 1), getattr(args, "tile_below", None))
+
+
 def build_render(args):
     """--render_worst K / --render_ids -> a Render for one pass, or None without either flag.  Both draw what --image_report lists: without
     it this is an error (the parser says so first; a namespace built by hand meets it here)."""
@@ -698,6 +781,7 @@ def main(args):
     build_image_report(args)                                            # --image_report without instances_<split>.json: an error before anything is built
     build_error_report(args)                                            # --error_report likewise
     build_bootstrap(args)                                               # --bootstrap_seed without --bootstrap, R out of range: likewise
+    build_tiling(args)                                                  # --tile_* without --tiles, too many virtual queries: likewise
     model, criterion, _ = counting_detr_amd.build_model(args)
     model.to(device)
     if args.resume:

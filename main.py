@@ -209,7 +209,8 @@ def main(args):
                                       device_detections=on_device, gt_json=gt_json if on_device and os.path.isfile(gt_json) else None,
                                       per_image=per_image, sweep=_infer.build_sweep(args), image_report=_infer.build_image_report(args, device),
                                       render=_infer.build_render(args), nms_iou=getattr(args, "nms_iou", None),
-                                      error_report=_infer.build_error_report(args, device), bootstrap=_infer.build_bootstrap(args, device))
+                                      error_report=_infer.build_error_report(args, device), bootstrap=_infer.build_bootstrap(args, device),
+                                      tiles=_infer.build_tiling(args))
             print("counting metrics ({}): {}".format(args.split, json.dumps(metrics)))
     if args.eval and args.synthetic:                                    # counting rule + MAE on the synthetic shard
         pred, gt = [], []
